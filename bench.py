@@ -15,6 +15,12 @@ those draws.  The steady state of repeating one configuration (items claimed by 
 measured costs, split samples started from RNG states an earlier draw recorded) is reported beside
 it as `warm_value` / `warm_ms_per_step`, never as `value`.
 
+A plain run does only what `value` needs: set up, `--warmup` untimed draws, `--steps` timed draws, the
+result line.  `--full` adds what takes runs of its own: the counting pass behind `roofline`, the warm
+leg (`warm_*`) and the CPU baseline (`cpu_baseline`); without it those keys are null or absent.
+`--dump-outputs DIR` writes what the last timed draw computed (frame buffers, 8-bit image, segment
+count) as DIR/*.npy; the inputs are fixed by the arguments, so two builds compare output for output.
+
 N > 1 (one process per GPU, torch.distributed over RCCL): rows are dealt in 4-row bands
 round-robin over ranks; each rank renders and resolves its rows for every fb; one all-gather of
 the 8-bit rows assembles the image.  Strong scaling (the image is fixed).
@@ -101,24 +107,70 @@ def parse():
     ap.add_argument("--no-step", action="store_true", help="segment-per-trip kernel even when the world is one BVH")
     ap.add_argument("--no-bins", action="store_true", help="camera rays traverse the BVH (no per-tile candidate lists)")
     ap.add_argument("--no-schedule", action="store_true", help="natural item order (no probe, no item schedule)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stats", action="store_true", help="skip the untimed node/prim counting pass")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="with --full: budget of the CPU-baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-stats", action="store_true",
+                    help="with --full: skip the untimed node/prim counting pass (no roofline)")
     ap.add_argument("--png", default="", help="write the assembled image (rank 0)")
-    ap.add_argument("--warm-steps", type=int, default=5,
-                    help="repeat draws timed after two priming draws (warm_*: the configuration's schedule and "
-                         "split-sample states reused; 0 = skip)")
+    ap.add_argument("--warm-steps", type=int, default=None,
+                    help="with --full: repeat draws timed after two priming draws (warm_*: the configuration's "
+                         "schedule and split-sample states reused; default 5, 0 = skip); a run without --full has "
+                         "no warm leg")
     ap.add_argument("--gather", default="rccl", choices=["rccl", "host"],
                     help="--gpus N without a launcher: ncclGather over distinct devices, or host copies (ranks may share a GPU)")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE",
                     help="context option (include/rt_hip.h rt_ctx_options), e.g. --opt shade_min=52; "
                          "one-process-per-GPU path only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the counting pass and the roofline, "
+                         "the warm leg (warm_*) and the CPU baseline; --no-stats, --warm-steps 0 and "
+                         "--no-cpu-baseline drop them one by one")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="debug: gloo runs the N>1 path with host-side collectives and ranks sharing the visible GPUs")
     a = ap.parse_args()
-    if a.steps < 1 or a.warmup < 0 or a.warm_steps < 0 or a.gpus < 1:
+    if a.steps < 1 or a.warmup < 0 or (a.warm_steps or 0) < 0 or a.gpus < 1:
         ap.error("--steps and --gpus must be >= 1, --warmup and --warm-steps >= 0")
+    if not a.full:  # a plain run: set up, warm up, time the steps, print the line
+        if a.warm_steps:
+            print(f"bench.py: --warm-steps {a.warm_steps} needs --full; this run has no warm leg", file=sys.stderr)
+        a.no_stats = a.no_cpu_baseline = True
+        a.warm_steps = 0
+    elif a.warm_steps is None:
+        a.warm_steps = 5
     return a
+
+
+DUMP_FB_ELEMS = 8 << 20     # float32 samples kept of the frame buffers (32 MB)
+DUMP_IMAGE_ELEMS = 4 << 20  # of the 8-bit image (16 MB as float32)
+
+
+def dump_sample(t, max_elems: int, seed: int):
+    """The flat tensor as float32 numpy: whole when it has at most max_elems elements, else the
+    elements at max_elems sorted indices drawn with a fixed seed (the same for every run and build)."""
+    import torch
+
+    t = t.reshape(-1)
+    if t.numel() > max_elems:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(0, t.numel(), (max_elems,), generator=g).sort().values
+        t = t[idx.to(t.device)]
+    return t.to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(dirname: str, fb, image, segments: int):
+    """--dump-outputs: what a caller of the timed path receives from its last step.  fb.npy: the float
+    frame buffers rt_render wrote (this rank's rows); image.npy: the assembled 8-bit image (rt_resolve
+    and the gather); segments.npy: the draw's segment count.  Large arrays as a seeded sample."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    if fb is not None:
+        np.save(os.path.join(dirname, "fb.npy"), dump_sample(fb, DUMP_FB_ELEMS, 1984))
+    np.save(os.path.join(dirname, "image.npy"), dump_sample(image, DUMP_IMAGE_ELEMS, 1985))
+    np.save(os.path.join(dirname, "segments.npy"), np.array([segments], np.float64))
 
 
 def parse_opts(items) -> dict:
@@ -409,6 +461,8 @@ def main():
         out = out_line(a, value, world, dt / a.steps, segs, roof, extra)
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a, a.cpu_seconds)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, fb, gathered if world > 1 else img[:len(rows) * a.width * 3], seg_step[0])
         print(json.dumps(out), flush=True)
         if a.png:
             from raytracing_gpu_amd import dist as rdist
@@ -485,6 +539,8 @@ def main_inprocess(a):
                        f"gather {'ncclGather (RCCL)' if mode == multi.RT_GATHER_RCCL else 'host copies'}; "
                        "a step includes the copy of the assembled image to the host"}
     out = out_line(a, value, a.gpus, dt / a.steps, segs, None, extra)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, None, torch.from_numpy(img), segs)
     print(json.dumps(out), flush=True)
     if a.png:
         rt.write_png(a.png, img)

@@ -29,7 +29,7 @@ run() {  # name timeout cmd...
 }
 bench() {  # name args...
   local name=$1; shift
-  run bench_$name 600 python -u bench.py "$@" ${BENCH_ARGS:-} || exit $?
+  run bench_$name 600 python -u bench.py --full "$@" ${BENCH_ARGS:-} || exit $?
   grep -o '"value": [0-9.]*\|"kernel_ms": [0-9.]*\|"warm_ms_per_step": [0-9.]*\|"warm_value": [0-9.]*\|"render_call_ms": [0-9.]*' \
     gpurun_out/bench_$name.log | tr '\n' ' '; echo
 }

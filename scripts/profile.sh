@@ -2,12 +2,12 @@
 # rocprofv3 passes for one bench workload: kernel trace + stats, then one PMC pass per counter
 # group (FETCH_SIZE and WRITE_SIZE do not fit one pass on gfx950; each pass its own run, never
 # combined with any trace domain).  Outputs under gpurun_out/${NAME}_*.
-#   NAME=c2 ARGS="--steps 2 --warmup 1 --no-cpu-baseline" bash scripts/profile.sh
+#   NAME=c2 ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline" bash scripts/profile.sh
 set -u
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 NAME=${NAME:-c2}
-ARGS=${ARGS:-"--steps 2 --warmup 1 --no-cpu-baseline"}
+ARGS=${ARGS:-"--full --steps 2 --warmup 1 --no-cpu-baseline"}
 step() { local name=$1; shift; timeout -k 10 ${STEP_TIMEOUT:-300} "$@" > gpurun_out/$name.log 2>&1; local rc=$?; echo "$name rc=$rc"; case $rc in 0) ;; *) exit $rc;; esac; }
 P="-d gpurun_out/${NAME}"
 step ${NAME}_trace rocprofv3 --kernel-trace --stats -d gpurun_out/${NAME}_trace -o run --output-format csv -- python bench.py $ARGS

@@ -1,6 +1,8 @@
 #!/bin/bash
 # rocprofv3 kernel trace + stats of bench.py exactly as the driver runs it (default arguments unless
-# ARGS is set): the summary whose render-kernel average the bench line's kernel_ms is checked against.
+# ARGS is set: a plain run, the warm-up and timed one-shot draws only; ARGS=--full adds the counting
+# pass and the warm leg): the summary whose render-kernel average the bench line's kernel_ms is
+# checked against.
 #   NAME=c2 bash scripts/trace_bench.sh
 set -u
 export TMPDIR=/tmp

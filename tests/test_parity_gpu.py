@@ -443,7 +443,7 @@ def test_bench_two_ranks_match_one(tmp_path):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["bench.py", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-stats",
+    common = ["bench.py", "--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-stats",
               "--width", "200", "--height", "112", "--spp", "2", "--nfb", "2"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     one = subprocess.run([sys.executable, *common, "--png", str(tmp_path / "n1.png")], cwd=root, env=env,
@@ -468,7 +468,7 @@ def test_bench_inprocess_two_ranks_match_one(tmp_path):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["bench.py", "--steps", "1", "--warmup", "1", "--warm-steps", "1", "--no-cpu-baseline",
+    common = ["bench.py", "--full", "--steps", "1", "--warmup", "1", "--warm-steps", "1", "--no-cpu-baseline",
               "--no-stats", "--width", "200", "--height", "112", "--spp", "2", "--nfb", "2"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
@@ -483,6 +483,42 @@ def test_bench_inprocess_two_ranks_match_one(tmp_path):
     assert line["n_gpus"] == 2 and "librt_multi.so" in line["driver"]
     assert line["value"] > 0 and line["warm_ms_per_step"] > 0
     assert (tmp_path / "n1.png").read_bytes() == (tmp_path / "n2.png").read_bytes()
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path, oracle):
+    """A plain `bench.py` run times exactly --steps draws and leaves the --full legs out of its line;
+    --dump-outputs writes the last timed draw's frame buffers (bit-identical to the oracle's), image and
+    segment count as float arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    W, H, spp, nfb = 64, 36, 2, 2
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--width", str(W),
+                        "--height", str(H), "--spp", str(spp), "--nfb", str(nfb), "--dump-outputs", str(out)],
+                       cwd=root, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
+    assert line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["roofline"] is None and line["warm_value"] is None and "cpu_baseline" not in line
+    fb = np.load(out / "fb.npy")
+    img = np.load(out / "image.npy")
+    segs = np.load(out / "segments.npy")
+    assert fb.dtype == np.float32 and fb.shape == (nfb * H * W * 3,)
+    assert img.dtype == np.float32 and img.shape == (H * W * 3,)
+    want_img, _, _ = oracle.draw("big1", W, H, spp, nfb)  # PNG order; the dump holds the rows bottom-up
+    assert np.array_equal(img.reshape(H, W, 3)[::-1], want_img.astype(np.float32))
+    ref = oracle.RefScene("big1")
+    total = 0
+    for f in range(nfb):
+        want, c, _ = ref.render(W, H, spp, f, 50, oracle.REF_CAM_REF_SLOT0)
+        total += c["segments"]
+        got = fb[f * H * W * 3:(f + 1) * H * W * 3]
+        assert np.array_equal(got.view(np.uint32), want.reshape(-1).view(np.uint32)), f"fb {f}"
+    assert segs.dtype == np.float64 and segs.tolist() == [float(total)] == [float(line["config"]["segments_per_step"])]
 
 
 def test_host_buffers_match_device(rtlib, gpu_ctx, oracle):
