@@ -10,9 +10,17 @@
 //     --depth D             max_depth (default 50)
 //     --obj PATH            mesh scenes: rt_obj_load (assimp's OBJ import, reference indexing)
 //     --tex PATH            texture for the mesh / earth scenes: rt_image_load (stb_image bytes)
+//     --progressive K       one GPU: draw through an rt_accum, K frame buffers per step; OUT.ppm is
+//                           rewritten after every step (the reference's tmp/<id>.ppm, render.h:152-162)
+//                           and each step prints one JSON line with "fbs_done"
+//     --checkpoint FILE     one GPU: save the accumulator to FILE after every step (one step of NO_FB
+//                           frame buffers without --progressive) and, when FILE exists, continue
+//                           from it up to NO_FB (prints a JSON line with "resumed_from")
 //
-// Writes OUT.ppm (binary P6, top row first) and one JSON line per draw on stdout.
+// Writes OUT.ppm (binary P6, top row first) and one JSON line per draw on stdout.  Files written
+// more than once go to a temporary name first and are renamed into place.
 #include <chrono>
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -55,12 +63,81 @@ std::vector<int> parse_devices(const char* s) {
   return d;
 }
 
+// Whole file to path: written under a temporary name, then renamed, so that a reader (or a run that
+// dies) never sees half a file.
+bool write_file(const std::string& path, const std::string& head, const void* data, size_t n) {
+  const std::string tmp = path + ".tmp";
+  FILE* f = fopen(tmp.c_str(), "wb");
+  if (!f) return false;
+  bool ok = fwrite(head.data(), 1, head.size(), f) == head.size() && fwrite(data, 1, n, f) == n;
+  ok = fclose(f) == 0 && ok;
+  return ok && rename(tmp.c_str(), path.c_str()) == 0;
+}
+
+bool read_file(const char* path, std::vector<unsigned char>& out) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  unsigned char buf[1 << 16];
+  for (size_t n; (n = fread(buf, 1, sizeof(buf), f)) > 0;) out.insert(out.end(), buf, buf + n);
+  fclose(f);
+  return true;
+}
+
+// draw() through an accumulator: `step` frame buffers at a time, OUT.ppm and the checkpoint
+// rewritten after each step.
+int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int step, const char* ckpt,
+                     const char* out, std::vector<uint8_t>& png) {
+  rt_accum* acc = nullptr;
+  std::vector<unsigned char> blob;
+  if (ckpt && read_file(ckpt, blob)) {
+    if (rt_accum_load(ctx, blob.data(), blob.size(), step, &acc)) return die("rt_accum_load", rt_last_error(ctx));
+    rt_accum_info i = {};
+    rt_accum_get_info(acc, &i);
+    const rt_render_args& b = i.args;
+    if (b.width != a.width || b.height != a.height || b.spp != a.spp || b.fb_first != a.fb_first ||
+        b.max_depth != a.max_depth || b.cam_mode != a.cam_mode || b.band_rows != a.band_rows ||
+        b.band_first != a.band_first || b.band_stride != a.band_stride || b.seed != a.seed || b.fb_count > a.fb_count)
+      return die("checkpoint", "belongs to a draw with other settings");
+    printf("{\"resumed_from\": %d, \"checkpoint\": \"%s\"}\n", b.fb_count, ckpt);
+    fflush(stdout);
+  } else if (rt_accum_create(ctx, &a, step, &acc)) {
+    return die("rt_accum_create", rt_last_error(ctx));
+  }
+  char head[64];
+  snprintf(head, sizeof(head), "P6\n%d %d\n255\n", a.width, a.height);
+  rt_accum_info i = {};
+  rt_accum_get_info(acc, &i);
+  for (bool first = true; first || i.args.fb_count < a.fb_count; first = false) {
+    const auto t0 = std::chrono::steady_clock::now();
+    rt_counters c = {};
+    const int n = std::min(step, a.fb_count - i.args.fb_count);
+    if (n > 0 && rt_accum_add(acc, n, &c)) return die("rt_accum_add", rt_last_error(ctx));
+    if (rt_accum_image(acc, png.data(), 1)) return die("rt_accum_image", rt_last_error(ctx));
+    rt_accum_get_info(acc, &i);
+    if (!write_file(out, head, png.data(), png.size())) return die("write", out);
+    if (ckpt && n > 0) {
+      size_t need = 0;
+      rt_accum_save(acc, nullptr, 0, &need);
+      blob.resize(need);
+      if (rt_accum_save(acc, blob.data(), blob.size(), nullptr)) return die("rt_accum_save", rt_last_error(ctx));
+      if (!write_file(ckpt, "", blob.data(), blob.size())) return die("write", ckpt);
+    }
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    printf("{\"fbs_done\": %d, \"scene\": \"%s\", \"width\": %d, \"height\": %d, \"wall_ms\": %.3f, "
+           "\"segments\": %llu, \"samples\": %llu}\n",
+           i.args.fb_count, name, a.width, a.height, ms, (unsigned long long)c.segments, (unsigned long long)c.samples);
+    fflush(stdout);
+  }
+  rt_accum_destroy(acc);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc < 6) {
     fprintf(stderr, "usage: rt_main SCENE WIDTH SPP_PER_FB NO_FB OUT.ppm [--devices 0,1] [--gather rccl|host] "
-                    "[--band-rows B] [--repeat K] [--depth D] [--obj PATH] [--tex PATH]\n");
+                    "[--band-rows B] [--repeat K] [--depth D] [--obj PATH] [--tex PATH] [--progressive K] [--checkpoint FILE]\n");
     return 2;
   }
   const char* name = argv[1];
@@ -71,7 +148,8 @@ int main(int argc, char** argv) {
   const char* out = argv[5];
   std::vector<int> devices;
   int gather = RT_GATHER_RCCL, band_rows = 4, repeat = 1;
-  const char *obj_path = nullptr, *tex_path = nullptr;
+  const char *obj_path = nullptr, *tex_path = nullptr, *ckpt_path = nullptr;
+  int progressive = 0;
   for (int k = 6; k < argc; ++k) {
     const std::string a = argv[k];
     const char* v = k + 1 < argc ? argv[k + 1] : "";
@@ -82,6 +160,8 @@ int main(int argc, char** argv) {
     else if (a == "--depth") s.max_depth = atoi(v), ++k;
     else if (a == "--obj") obj_path = v, ++k;
     else if (a == "--tex") tex_path = v, ++k;
+    else if (a == "--progressive") progressive = atoi(v), ++k;
+    else if (a == "--checkpoint") ckpt_path = v, ++k;
     else return die("unknown option", argv[k]);
   }
 
@@ -140,6 +220,14 @@ int main(int argc, char** argv) {
     int rc = rt_multi_create((int)devices.size(), devices.data(), gather, &multi);
     if (rc) return die("rt_multi_create", gather == RT_GATHER_RCCL ? "RCCL communicator (distinct devices?)" : "");
     if (rt_multi_upload(multi, soa)) return die("rt_multi_upload", rt_multi_last_error(multi));
+  }
+  if (progressive != 0 || ckpt_path) {
+    if (!ctx) return die("--progressive / --checkpoint", "one GPU only (no --devices)");
+    if (progressive < 0 || a.fb_count < 1) return die("--progressive", "K and NO_FB must be at least 1");
+    const int rc = draw_progressive(ctx, name, a, progressive > 0 ? progressive : a.fb_count, ckpt_path, out, png);
+    rt_ctx_destroy(ctx);
+    rt_scene_free(scene);
+    return rc;
   }
   for (int k = 0; k < repeat; ++k) {
     const auto t0 = std::chrono::steady_clock::now();

@@ -324,6 +324,54 @@ int rt_resolve(rt_ctx* ctx, const rt_render_args* args, const float* fb, uint8_t
  * (top row first), W*H*3 bytes.  counters may be NULL. */
 int rt_draw(rt_ctx* ctx, const rt_render_args* args, uint8_t* png_rgb_host, rt_counters* counters);
 
+/* ------------------------------------------------------------------ progressive accumulator */
+/* draw() one frame buffer at a time (render.h:152-162 writes tmp/<id>.ppm after each fb,
+ * average_images folds the files at the end, color.h:57-170).  The image of k frame buffers is
+ * quant(sum / k) with sum += float(c*c) / (255*255) per fb in fb order, so the float sums and the
+ * count are the whole state: an accumulator can be previewed, saved and continued after any fb, and
+ * continuing is bit-identical to never having stopped.  An accumulator belongs to its context (and
+ * must be destroyed before it); it holds owned_rows x width x 3 float sums and a float frame-buffer
+ * scratch of chunk_fbs frame buffers, nothing else. */
+typedef struct rt_accum rt_accum;
+typedef struct rt_accum_info {
+  rt_render_args args;    /* as given to rt_accum_create; fb_count = frame buffers folded in so far */
+  int64_t n_values;       /* owned_rows x width x 3                                              */
+  uint64_t scene_fp;      /* FNV-1a of the uploaded scene's arrays, camera and background         */
+} rt_accum_info;
+
+/* args fixes width, height, spp, max_depth, cam_mode, flags, seed and the band tiling; fb_first is
+ * the first fb id, fb_count is ignored.  chunk_fbs >= 1: frame buffers per rt_render launch. */
+int rt_accum_create(rt_ctx* ctx, const rt_render_args* args, int32_t chunk_fbs, rt_accum** out);
+/* Renders the next `count` fb ids (rt_render, at most chunk_fbs per launch) and folds them in.
+ * counters may be NULL; it receives this call's totals.  RT_ERR_STATE after another rt_scene_upload. */
+int rt_accum_add(rt_accum* acc, int32_t count, rt_counters* counters);
+/* Folds in `count` frame buffers the caller rendered: [count][owned_rows][width][3] floats, device
+ * or host pointer. */
+int rt_accum_add_fbs(rt_accum* acc, const float* fb, int32_t count);
+/* Image of the frame buffers folded in so far.  png_order = 0: rt_resolve's layout (owned rows
+ * ascending, device or host out).  png_order = 1: rt_draw's (whole-image tiling only, top row first,
+ * host out).  RT_ERR_STATE with no frame buffer yet. */
+int rt_accum_image(rt_accum* acc, uint8_t* out, int32_t png_order);
+int rt_accum_get_info(const rt_accum* acc, rt_accum_info* info);
+/* Device time in ms, from HIP events on the context stream, of the last accumulate launch (the last
+ * chunk of rt_accum_add, or rt_accum_add_fbs) and of the last rt_accum_image's kernel; 0 before one. */
+float rt_accum_last_add_ms(const rt_accum* acc);
+float rt_accum_last_image_ms(const rt_accum* acc);
+int rt_accum_destroy(rt_accum* acc);
+/* Checkpoint blob (little-endian): 8 bytes magic "RTACCUM1", u32 version (1), u32 header size (96),
+ * the 13 rt_render_args fields in order (12 x i32, u64 seed), i64 n_values, u64 scene_fp,
+ * u64 FNV-1a of the payload; then n_values float sums.  rt_accum_save writes *need (may be NULL)
+ * and, when cap >= need, the blob (blob = NULL with cap = 0 asks for the size); a smaller cap is
+ * RT_ERR_ARG.  rt_accum_load returns RT_ERR_STATE when the context's scene differs from the blob's. */
+int rt_accum_save(rt_accum* acc, void* blob, size_t cap, size_t* need);
+int rt_accum_load(rt_ctx* ctx, const void* blob, size_t n, int32_t chunk_fbs, rt_accum** out);
+/* Host only (no context, no GPU; csrc/rt_accum_blob.cpp): validate a blob (magic, version, size
+ * against n_values and the tiling, checksum) and fill info; finalise it into the 8-bit image
+ * (rt_resolve's layout, n_values bytes); build a blob from an info and its float sums. */
+int rt_accum_blob_info(const void* blob, size_t n, rt_accum_info* info);
+int rt_accum_blob_image(const void* blob, size_t n, uint8_t* out);
+int rt_accum_blob_pack(const rt_accum_info* info, const float* sums, void* blob, size_t cap, size_t* need);
+
 /* ------------------------------------------------------------------ host scene library */
 /* Builds one of the reference scenes (scenes.h) on the host: "basic", "first", "big1" (alias
  * "random"), "two_spheres", "two_perlin", "cornell", "cornell_smoke", "triangle", "triangles",

@@ -7,6 +7,9 @@ Host mirror of the reference's interface for that path (names and argument meani
   * ``scene`` / ``Scene.builtin(name)`` — struct scene and its subclasses, scenes.h:36-621
   * ``draw(scene, settings)`` — render.h:118-174 (render_init, no_fb render launches, per-fb
     quantise + square-average); returns the PNG raster instead of writing ./image.png
+  * ``draw_progressive(scene, settings, every=..., on_image=..., checkpoint=...)`` — the same draw
+    cut after any frame buffer (the reference keeps tmp/<id>.ppm per fb, render.h:152-162):
+    previews, stop and resume through ``Context.accumulator`` / ``Accumulator`` / ``read_checkpoint``
   * ``Context.render_init / render / resolve`` — the kernels render_init (render.h:84-92) and
     render (render.h:94-113) behind the C ABI of include/rt_hip.h
 
@@ -18,7 +21,7 @@ from __future__ import annotations
 import ctypes
 import sys
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_uint8, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint64, c_void_p
 from dataclasses import dataclass
 
 import numpy as np
@@ -126,6 +129,17 @@ class rt_counters(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class rt_accum_info(ctypes.Structure):
+    """include/rt_hip.h rt_accum_info: args.fb_count = frame buffers folded in so far."""
+    _fields_ = [("args", rt_render_args), ("n_values", c_int64), ("scene_fp", c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self.args, k)) for k, _ in rt_render_args._fields_}
+        d["n_values"] = int(self.n_values)
+        d["scene_fp"] = int(self.scene_fp)
+        return d
+
+
 # Every entry point of include/rt_hip.h: name -> (restype, argtypes)
 ABI = {
     "rt_ctx_create": (c_int, [c_int, POINTER(c_void_p)]),
@@ -146,6 +160,19 @@ ABI = {
     "rt_audit_log": (c_int, [c_void_p, POINTER(c_float), c_int32]),
     "rt_resolve": (c_int, [c_void_p, POINTER(rt_render_args), c_void_p, c_void_p]),
     "rt_draw": (c_int, [c_void_p, POINTER(rt_render_args), POINTER(c_uint8), POINTER(rt_counters)]),
+    "rt_accum_create": (c_int, [c_void_p, POINTER(rt_render_args), c_int32, POINTER(c_void_p)]),
+    "rt_accum_add": (c_int, [c_void_p, c_int32, POINTER(rt_counters)]),
+    "rt_accum_add_fbs": (c_int, [c_void_p, c_void_p, c_int32]),
+    "rt_accum_image": (c_int, [c_void_p, c_void_p, c_int32]),
+    "rt_accum_get_info": (c_int, [c_void_p, POINTER(rt_accum_info)]),
+    "rt_accum_last_add_ms": (c_float, [c_void_p]),
+    "rt_accum_last_image_ms": (c_float, [c_void_p]),
+    "rt_accum_destroy": (c_int, [c_void_p]),
+    "rt_accum_save": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]),
+    "rt_accum_load": (c_int, [c_void_p, c_void_p, c_size_t, c_int32, POINTER(c_void_p)]),
+    "rt_accum_blob_info": (c_int, [c_void_p, c_size_t, POINTER(rt_accum_info)]),
+    "rt_accum_blob_image": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "rt_accum_blob_pack": (c_int, [POINTER(rt_accum_info), c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]),
     "rt_scene_build": (c_int, [c_char_p, POINTER(c_void_p)]),
     "rt_scene_build_ex": (c_int, [c_char_p, c_void_p, POINTER(c_void_p)]),
     "rt_obj_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
@@ -184,8 +211,15 @@ def lib() -> ctypes.CDLL:
     return _lib
 
 
+RT_OK, RT_ERR_ARG, RT_ERR_HIP, RT_ERR_STATE, RT_ERR_SCENE, RT_ERR_NOMEM = range(6)
+
+
 class RtError(RuntimeError):
-    pass
+    """A nonzero rt_status of the C ABI (`status`; None where no call returned one)."""
+
+    def __init__(self, msg: str, status: int | None = None):
+        super().__init__(msg)
+        self.status = status
 
 
 # ---------------------------------------------------------------- render_settings (render.h:21-50)
@@ -316,7 +350,7 @@ class Context:
     def _check(self, rc: int, what: str) -> None:
         if rc != 0:
             msg = lib().rt_last_error(self._c)
-            raise RtError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            raise RtError(f"{what} failed ({rc}): {msg.decode() if msg else ''}", rc)
 
     def options(self) -> dict:
         o = rt_ctx_options()
@@ -400,7 +434,17 @@ class Context:
                                   ctypes.byref(cnt)), "rt_draw")
         return img, cnt.as_dict()
 
+    def accumulator(self, args: rt_render_args, chunk_fbs: int = 1) -> "Accumulator":
+        """A progressive draw of args' configuration starting at args.fb_first (args.fb_count is
+        ignored): frame buffers are rendered chunk_fbs per launch and folded into float sums on the
+        device; see Accumulator."""
+        h = c_void_p()
+        self._check(lib().rt_accum_create(self._c, ctypes.byref(args), chunk_fbs, ctypes.byref(h)), "rt_accum_create")
+        return Accumulator(self, h)
+
     def close(self) -> None:
+        for acc in list(getattr(self, "_accums", ())):  # an accumulator does not outlive its context
+            acc.close()
         if getattr(self, "_c", None):
             lib().rt_ctx_destroy(self._c)
             self._c = None
@@ -410,6 +454,168 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+class Accumulator:
+    """rt_accum of include/rt_hip.h: draw() one frame buffer at a time.  The reference writes
+    tmp/<id>.ppm after each frame buffer (render.h:152-162) and folds the files at the end
+    (average_images, color.h:57-170); here the float sums stay on the device, so after any add()
+    there is an image(), and save() / load() continue bit-identically in another process."""
+
+    def __init__(self, ctx: Context, handle: c_void_p):
+        import weakref
+
+        self.ctx = ctx
+        self._h = handle
+        if not hasattr(ctx, "_accums"):
+            ctx._accums = weakref.WeakSet()
+        ctx._accums.add(self)
+
+    @classmethod
+    def load(cls, ctx: Context, path: str, chunk_fbs: int = 1) -> "Accumulator":
+        """Continue from a checkpoint file; RtError with status RT_ERR_STATE when the context's scene
+        is not the one the checkpoint was rendered from, RT_ERR_ARG for a malformed file."""
+        with open(path, "rb") as f:
+            blob = f.read()
+        h = c_void_p()
+        ctx._check(lib().rt_accum_load(ctx._c, blob, len(blob), chunk_fbs, ctypes.byref(h)), "rt_accum_load")
+        return cls(ctx, h)
+
+    def info(self) -> dict:
+        i = rt_accum_info()
+        self.ctx._check(lib().rt_accum_get_info(self._h, ctypes.byref(i)), "rt_accum_get_info")
+        return i.as_dict()
+
+    @property
+    def done(self) -> int:
+        """Frame buffers folded in so far."""
+        return self.info()["fb_count"]
+
+    def add(self, count: int = 1) -> dict:
+        """Render and fold in the next count frame buffers; returns this call's counters."""
+        self.ctx._after_torch()
+        cnt = rt_counters()
+        self.ctx._check(lib().rt_accum_add(self._h, count, ctypes.byref(cnt)), "rt_accum_add")
+        return cnt.as_dict()
+
+    def add_fbs(self, ptr: int, count: int) -> None:
+        """Fold in count frame buffers [count][owned_rows][width][3] float32 at a device or host address."""
+        self.ctx._after_torch()
+        self.ctx._check(lib().rt_accum_add_fbs(self._h, c_void_p(ptr), count), "rt_accum_add_fbs")
+
+    def image(self, png_order: bool = False) -> np.ndarray:
+        """The image so far: (owned_rows, width, 3) uint8, owned rows ascending (rt_resolve's layout), or
+        with png_order the whole image top row first (rt_draw's)."""
+        i = self.info()
+        img = np.zeros((i["n_values"] // (3 * i["width"]), i["width"], 3), np.uint8)
+        self.ctx._check(lib().rt_accum_image(self._h, img.ctypes.data, 1 if png_order else 0), "rt_accum_image")
+        return img
+
+    def image_into(self, out_ptr: int, png_order: bool = False) -> None:
+        """image() into caller memory (a device address with png_order False, or a host address)."""
+        self.ctx._after_torch()
+        self.ctx._check(lib().rt_accum_image(self._h, c_void_p(out_ptr), 1 if png_order else 0), "rt_accum_image")
+
+    def last_add_ms(self) -> float:
+        """Device time of the last accumulate launch (the last chunk of add(), or add_fbs())."""
+        return float(lib().rt_accum_last_add_ms(self._h))
+
+    def last_image_ms(self) -> float:
+        """Device time of the last image() kernel."""
+        return float(lib().rt_accum_last_image_ms(self._h))
+
+    def blob(self) -> bytes:
+        need = c_size_t()
+        self.ctx._check(lib().rt_accum_save(self._h, None, 0, ctypes.byref(need)), "rt_accum_save")
+        buf = ctypes.create_string_buffer(need.value)
+        self.ctx._check(lib().rt_accum_save(self._h, buf, need.value, None), "rt_accum_save")
+        return buf.raw
+
+    def save(self, path: str) -> None:
+        """Write the checkpoint to path: to a temporary name beside it first, then renamed over it."""
+        tmp = f"{path}.tmp{os.getpid()}"
+        with open(tmp, "wb") as f:
+            f.write(self.blob())
+        os.replace(tmp, path)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_c", None):
+                lib().rt_accum_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def read_checkpoint(path: str) -> tuple[dict, np.ndarray]:
+    """(info, image) of a checkpoint file, by the host-only rt_accum_blob_* functions (no context, no
+    GPU): info as Accumulator.info(), image (owned_rows, width, 3) uint8 with owned rows ascending
+    (bottom row first for a whole image)."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    i = rt_accum_info()
+    rc = lib().rt_accum_blob_info(blob, len(blob), ctypes.byref(i))
+    if rc != 0:
+        raise RtError(f"rt_accum_blob_info({path!r}) failed ({rc})", rc)
+    d = i.as_dict()
+    img = np.zeros((d["n_values"] // (3 * d["width"]), d["width"], 3), np.uint8)
+    rc = lib().rt_accum_blob_image(blob, len(blob), img.ctypes.data)
+    if rc != 0:
+        raise RtError(f"rt_accum_blob_image({path!r}) failed ({rc})", rc)
+    return d, img
+
+
+def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context | None = None, every: int = 1,
+                     on_image=None, checkpoint: str | None = None, chunk_fbs: int | None = None,
+                     cam_mode: int = RT_CAM_REF_SLOT0, seed: int = 1984) -> tuple[np.ndarray, dict]:
+    """draw() of render.h:118-174 in steps of `every` frame buffers: after each step
+    on_image(image, fbs_done) gets the PNG-order image so far (the reference leaves tmp/<id>.ppm
+    behind, render.h:152-162) and, with a checkpoint path, the state is saved there (temporary name,
+    then rename).  An existing checkpoint of the same scene and settings is continued; one of another
+    scene or other settings raises.  Returns (final image, counters of the frame buffers rendered by
+    this call); the image is byte-identical to draw()'s.  chunk_fbs: frame buffers per render launch
+    (default: every)."""
+    if settings.image_height <= 0:
+        settings.aspect_ratio = curr_scene.aspect
+        settings.calc_all()
+    if every < 1:
+        raise ValueError("every < 1")
+    own = ctx is None
+    ctx = ctx or Context(0)
+    acc = None
+    try:
+        ctx.upload(curr_scene)
+        args = make_args(settings.image_width, settings.image_height, settings.samples_per_pixel_per_fb,
+                         0, 1, settings.max_depth, cam_mode, seed=seed)
+        chunk = chunk_fbs or every
+        if checkpoint and os.path.exists(checkpoint):
+            acc = Accumulator.load(ctx, checkpoint, chunk)
+            got, want = acc.info(), rt_accum_info(args, 0, 0).as_dict()
+            differ = [k for k in want if k not in ("fb_count", "n_values", "scene_fp") and got[k] != want[k]]
+            if differ or got["fb_count"] > settings.no_fb:
+                raise RtError(f"checkpoint {checkpoint!r} is of another draw: {differ or 'more frame buffers'}")
+        else:
+            acc = ctx.accumulator(args, chunk)
+        total = rt_counters().as_dict()
+        img = acc.image(png_order=True) if acc.done else None
+        while acc.done < settings.no_fb:
+            cnt = acc.add(min(every, settings.no_fb - acc.done))
+            total = {k: total[k] + cnt[k] for k in total}
+            img = acc.image(png_order=True)
+            if checkpoint:
+                acc.save(checkpoint)
+            if on_image is not None:
+                on_image(img, acc.done)
+        return img, total
+    finally:
+        if acc is not None:
+            acc.close()
+        if own:
+            ctx.close()
 
 
 def draw(curr_scene: Scene, settings: render_settings, ctx: Context | None = None,

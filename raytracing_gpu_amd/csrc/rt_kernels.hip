@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/rt_hip.h"
+#include "rt_accum_blob.h"
 #include "rt_detmath.h"
 #include "rt_diag.h"
 #include "rt_host_geom.h"
@@ -2674,6 +2675,63 @@ __global__ __launch_bounds__(kBlock) void resolve_kernel(const float* __restrict
   out[k] = (uint8_t)quant(acc / (float)nfb);
 }
 
+// Progressive accumulator (rt_accum): resolve_kernel's sum kept in memory between launches, so that
+// it can be cut after any frame buffer.  Element k: a = sums[k]; a += float(c*c) / (255*255) for
+// c = quant(fb[f][k]), f = 0..nfb-1 in order; sums[k] = a -- the same float operations in the same
+// order as resolve_kernel's acc (the sums start at 0.0f as acc does).
+// A pure stream: a lane owns 4 consecutive elements.  VEC (per_fb % 4 == 0, fb and sums 16-byte
+// aligned, so every frame buffer's start f*per_fb is too): one 16-byte load per frame buffer, one
+// 16-byte load and store of the sums, consecutive lanes on consecutive 16 bytes; elements past the
+// last whole group of 4, and everything when !VEC (odd per_fb, an offset fb pointer), go one by one.
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void accum_add_kernel(const float* __restrict__ fb, float* __restrict__ sums,
+                                                          long long per_fb, int nfb) {
+  const long long k0 = 4 * ((long long)blockIdx.x * kBlock + threadIdx.x);
+  if (k0 >= per_fb) return;
+  if (VEC && k0 + 4 <= per_fb) {
+    float4 a = *reinterpret_cast<const float4*>(sums + k0);
+#pragma unroll 4
+    for (int f = 0; f < nfb; ++f) {
+      const float4 v = *reinterpret_cast<const float4*>(fb + (long long)f * per_fb + k0);
+      const int cx = quant(v.x), cy = quant(v.y), cz = quant(v.z), cw = quant(v.w);
+      a.x += (float)(cx * cx) / (255.0f * 255.0f);
+      a.y += (float)(cy * cy) / (255.0f * 255.0f);
+      a.z += (float)(cz * cz) / (255.0f * 255.0f);
+      a.w += (float)(cw * cw) / (255.0f * 255.0f);
+    }
+    *reinterpret_cast<float4*>(sums + k0) = a;
+    return;
+  }
+  const long long k1 = k0 + 4 < per_fb ? k0 + 4 : per_fb;
+  for (long long k = k0; k < k1; ++k) {
+    float a = sums[k];
+    for (int f = 0; f < nfb; ++f) {
+      const int c = quant(fb[(long long)f * per_fb + k]);
+      a += (float)(c * c) / (255.0f * 255.0f);
+    }
+    sums[k] = a;
+  }
+}
+
+// The image of the nfb frame buffers folded into sums: resolve_kernel's last line.  VEC (sums 16-byte,
+// out 4-byte aligned): 4 sums in, 4 bytes out per lane.
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void accum_image_kernel(const float* __restrict__ sums, uint8_t* __restrict__ out,
+                                                            long long n, int nfb) {
+  const long long k0 = 4 * ((long long)blockIdx.x * kBlock + threadIdx.x);
+  if (k0 >= n) return;
+  const float d = (float)nfb;
+  if (VEC && k0 + 4 <= n) {
+    const float4 a = *reinterpret_cast<const float4*>(sums + k0);
+    const uint32_t q = (uint32_t)quant(a.x / d) | (uint32_t)quant(a.y / d) << 8 | (uint32_t)quant(a.z / d) << 16 |
+                       (uint32_t)quant(a.w / d) << 24;
+    *reinterpret_cast<uint32_t*>(out + k0) = q;
+    return;
+  }
+  const long long k1 = k0 + 4 < n ? k0 + 4 : n;
+  for (long long k = k0; k < k1; ++k) out[k] = (uint8_t)quant(sums[k] / d);
+}
+
 // Split items (render_step_kernel split_mode 2): the fb value of each of the first n_split items
 // of perm from its samples' sums, added in sample order from 0 -- the same float additions as the
 // item's own loop (col = 0; col += sample sum; (0 + x) + y == x + y for every x that is not -0,
@@ -3007,6 +3065,7 @@ struct rt_ctx {
   long long sort_scratch_cap = 0;
   long long cam_st_key[3] = {-1, -1, -1};
   long long scene_gen = 0;
+  uint64_t scene_fp = 0;  // rtacc::scene_fingerprint of the uploaded scene (accumulator checkpoints)
   int cus = 0, blocks_per_cu[32] = {0};  // per kernel variant (kVariants)
   int features = 0;
   bool world_bvh = false;  // the world list is one BVH object (camera tile lists apply)
@@ -4125,6 +4184,9 @@ int rt_scene_upload(rt_ctx* c, const rt_scene_soa* s) {
     if (s->prims[k].material < 0 || s->prims[k].material >= s->n_materials)
       return fail(c, RT_ERR_SCENE, "prim material out of range");
   free_scene(c);
+  // the fingerprint accumulator checkpoints are tied to (byte-serial FNV-1a over the caller's arrays,
+  // which the context does not keep: 0.6 GB/s on the host)
+  c->scene_fp = rtacc::scene_fingerprint(s);
   // Device copies: primitives with the u,v flag folded into the type word and their reference
   // leaf rank in p[9]; nodes = reference trees followed by the traversal trees built here.
   std::vector<rt_prim> prims(s->prims, s->prims + s->n_prims);
@@ -4974,6 +5036,278 @@ int rt_draw(rt_ctx* c, const rt_render_args* a, uint8_t* png_rgb_host, rt_counte
   if (rc) return rc;
   const size_t row = (size_t)a->width * 3;
   for (int j = 0; j < a->height; ++j) memcpy(png_rgb_host + (size_t)(a->height - 1 - j) * row, tmp.data() + j * row, row);
+  return RT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------- progressive accumulator
+// draw() cut after any frame buffer: the float sums of average_images (color.h:57-170) stay on the
+// device between calls, the frame buffers of one chunk at a time go through `scratch`.
+struct rt_accum {
+  rt_ctx* ctx = nullptr;
+  rt_render_args args{};  // fb_count = frame buffers folded in
+  int32_t chunk = 1;
+  long long per_fb = 0;   // owned_rows x width x 3
+  long long scene_gen = 0;
+  uint64_t scene_fp = 0;
+  float* sums = nullptr;     // [per_fb]
+  float* scratch = nullptr;  // [chunk][per_fb], allocated by the first rt_accum_add
+  uint8_t* img = nullptr;    // [per_fb], allocated by the first rt_accum_image into host memory
+  // around the last accumulate launch (ev[0], ev[1]) and the last image launch (ev[2], ev[3])
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool add_timed = false, image_timed = false;
+};
+
+extern "C" int rt_accum_destroy(rt_accum* acc);
+
+namespace {
+
+bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+// sums += the count frame buffers at fb_dev, queued on the context's stream.
+int accum_fold(rt_accum* acc, const float* fb_dev, int count) {
+  rt_ctx* c = acc->ctx;
+  const long long per_fb = acc->per_fb;
+  const unsigned blocks = (unsigned)(((per_fb + 3) / 4 + kBlock - 1) / kBlock);
+  HIPCHK(c, hipEventRecord(acc->ev[0], c->stream));
+  if (per_fb % 4 == 0 && aligned_to(fb_dev, 16) && aligned_to(acc->sums, 16))
+    hipLaunchKernelGGL(accum_add_kernel<true>, dim3(blocks), dim3(kBlock), 0, c->stream, fb_dev, acc->sums, per_fb, count);
+  else
+    hipLaunchKernelGGL(accum_add_kernel<false>, dim3(blocks), dim3(kBlock), 0, c->stream, fb_dev, acc->sums, per_fb, count);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(acc->ev[1], c->stream));
+  acc->add_timed = true;
+  acc->args.fb_count += count;
+  return RT_OK;
+}
+
+int accum_new(rt_ctx* c, const rt_render_args* a, int32_t chunk_fbs, rt_accum** out) {
+  if (!c) return RT_ERR_ARG;
+  if (!out) return fail(c, RT_ERR_ARG, "null accumulator pointer");
+  *out = nullptr;
+  if (!a) return fail(c, RT_ERR_ARG, "null args");
+  rt_render_args one = *a;
+  one.fb_count = 1;
+  const int rc = validate_args(c, &one);
+  if (rc) return rc;
+  if (chunk_fbs < 1) return fail(c, RT_ERR_ARG, "chunk_fbs < 1");
+  if (a->fb_first > INT32_MAX - chunk_fbs) return fail(c, RT_ERR_ARG, "fb range overflows");
+  const long long per_fb = (long long)rt_owned_rows(a, nullptr) * a->width * 3;
+  if (per_fb <= 0) return fail(c, RT_ERR_ARG, "no rows owned");
+  if (!c->have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
+  HIPCHK(c, hipSetDevice(c->device));
+  rt_accum* acc = new rt_accum;
+  acc->ctx = c;
+  acc->args = *a;
+  acc->args.fb_count = 0;
+  acc->chunk = chunk_fbs;
+  acc->per_fb = per_fb;
+  acc->scene_gen = c->scene_gen;
+  acc->scene_fp = c->scene_fp;
+  for (hipEvent_t& e : acc->ev)
+    if (hipEventCreate(&e) != hipSuccess) {
+      e = nullptr;
+      rt_accum_destroy(acc);
+      return fail(c, RT_ERR_HIP, "hipEventCreate");
+    }
+  if (hipMalloc((void**)&acc->sums, (size_t)per_fb * sizeof(float)) != hipSuccess) {
+    acc->sums = nullptr;
+    rt_accum_destroy(acc);
+    return fail(c, RT_ERR_NOMEM, "hipMalloc accumulator sums");
+  }
+  if (hipMemsetAsync(acc->sums, 0, (size_t)per_fb * sizeof(float), c->stream) != hipSuccess) {
+    rt_accum_destroy(acc);
+    return fail(c, RT_ERR_HIP, "clear accumulator sums");
+  }
+  *out = acc;
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_accum_create(rt_ctx* c, const rt_render_args* a, int32_t chunk_fbs, rt_accum** out) {
+  return accum_new(c, a, chunk_fbs, out);
+}
+
+int rt_accum_destroy(rt_accum* acc) {
+  if (!acc) return RT_ERR_ARG;
+  (void)hipSetDevice(acc->ctx->device);
+  (void)hipStreamSynchronize(acc->ctx->stream);
+  if (acc->sums) (void)hipFree(acc->sums);
+  if (acc->scratch) (void)hipFree(acc->scratch);
+  if (acc->img) (void)hipFree(acc->img);
+  for (hipEvent_t e : acc->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete acc;
+  return RT_OK;
+}
+
+int rt_accum_add(rt_accum* acc, int32_t count, rt_counters* counters) {
+  if (!acc) return RT_ERR_ARG;
+  rt_ctx* c = acc->ctx;
+  if (count < 1) return fail(c, RT_ERR_ARG, "count < 1");
+  if (count > INT32_MAX - acc->args.fb_first - acc->args.fb_count) return fail(c, RT_ERR_ARG, "fb range overflows");
+  if (acc->scene_gen != c->scene_gen) return fail(c, RT_ERR_STATE, "scene uploaded again since the accumulator was created");
+  HIPCHK(c, hipSetDevice(c->device));
+  const rt_render_args& a = acc->args;
+  // the RNG states of (W, H, seed), as rt_draw makes them (rendering leaves them as they are)
+  if (!c->states || c->states_n != (long long)a.width * a.height || c->states_seed != a.seed) {
+    const int rc = rt_render_init(c, a.width, a.height, a.seed);
+    if (rc) return rc;
+  }
+  if (!acc->scratch && hipMalloc((void**)&acc->scratch, (size_t)acc->chunk * acc->per_fb * sizeof(float)) != hipSuccess) {
+    acc->scratch = nullptr;
+    return fail(c, RT_ERR_NOMEM, "hipMalloc accumulator frame buffers");
+  }
+  rt_counters total = {};
+  for (int32_t left = count; left > 0;) {
+    const int32_t n = std::min(left, acc->chunk);
+    rt_render_args r = a;
+    r.fb_first = a.fb_first + a.fb_count;
+    r.fb_count = n;
+    rt_counters cnt = {};
+    int rc = rt_render(c, &r, acc->scratch, &cnt);
+    if (!rc) rc = accum_fold(acc, acc->scratch, n);  // ordered before the next chunk's render on the stream
+    if (rc) return rc;
+    total.segments += cnt.segments;
+    total.node_tests += cnt.node_tests;
+    total.prim_tests += cnt.prim_tests;
+    total.samples += cnt.samples;
+    total.fallbacks += cnt.fallbacks;
+    left -= n;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (counters) *counters = total;
+  return RT_OK;
+}
+
+int rt_accum_add_fbs(rt_accum* acc, const float* fb, int32_t count) {
+  if (!acc) return RT_ERR_ARG;
+  rt_ctx* c = acc->ctx;
+  if (!fb) return fail(c, RT_ERR_ARG, "null fb");
+  if (count < 1) return fail(c, RT_ERR_ARG, "count < 1");
+  if (count > INT32_MAX - acc->args.fb_first - acc->args.fb_count) return fail(c, RT_ERR_ARG, "fb range overflows");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = RT_OK;
+  float* tmp = nullptr;  // a host frame buffer is staged through device memory, as rt_resolve does
+  if (!device_ptr(fb)) {
+    const size_t bytes = (size_t)count * acc->per_fb * sizeof(float);
+    if (hipMalloc((void**)&tmp, bytes) != hipSuccess) return fail(c, RT_ERR_NOMEM, "hipMalloc frame buffer staging");
+    if (hipMemcpy(tmp, fb, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, RT_ERR_HIP, "copy frame buffer to device");
+  }
+  if (!rc) rc = accum_fold(acc, tmp ? tmp : fb, count);
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(c, RT_ERR_HIP, "accumulate kernel");
+  if (tmp) (void)hipFree(tmp);
+  return rc;
+}
+
+int rt_accum_image(rt_accum* acc, uint8_t* out, int32_t png_order) {
+  if (!acc) return RT_ERR_ARG;
+  rt_ctx* c = acc->ctx;
+  if (!out) return fail(c, RT_ERR_ARG, "null image");
+  if (png_order != 0 && png_order != 1) return fail(c, RT_ERR_ARG, "bad png_order");
+  const rt_render_args& a = acc->args;
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool out_dev = device_ptr(out);
+  if (png_order && acc->per_fb != (long long)a.width * a.height * 3)
+    return fail(c, RT_ERR_ARG, "png_order needs the whole-image tiling");
+  if (png_order && out_dev) return fail(c, RT_ERR_ARG, "png_order needs a host image");
+  if (a.fb_count < 1) return fail(c, RT_ERR_STATE, "no frame buffer accumulated yet");
+  if (!out_dev && !acc->img && hipMalloc((void**)&acc->img, (size_t)acc->per_fb) != hipSuccess) {
+    acc->img = nullptr;
+    return fail(c, RT_ERR_NOMEM, "hipMalloc accumulator image");
+  }
+  uint8_t* img = out_dev ? out : acc->img;
+  const unsigned blocks = (unsigned)(((acc->per_fb + 3) / 4 + kBlock - 1) / kBlock);
+  HIPCHK(c, hipEventRecord(acc->ev[2], c->stream));
+  if (aligned_to(acc->sums, 16) && aligned_to(img, 4))
+    hipLaunchKernelGGL(accum_image_kernel<true>, dim3(blocks), dim3(kBlock), 0, c->stream, acc->sums, img, acc->per_fb, a.fb_count);
+  else
+    hipLaunchKernelGGL(accum_image_kernel<false>, dim3(blocks), dim3(kBlock), 0, c->stream, acc->sums, img, acc->per_fb, a.fb_count);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(acc->ev[3], c->stream));
+  acc->image_timed = true;
+  if (out_dev) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+  }
+  if (!png_order) {
+    HIPCHK(c, hipMemcpyAsync(out, img, (size_t)acc->per_fb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+  }
+  std::vector<uint8_t> tmp((size_t)acc->per_fb);
+  HIPCHK(c, hipMemcpyAsync(tmp.data(), img, tmp.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t row = (size_t)a.width * 3;
+  for (int j = 0; j < a.height; ++j) memcpy(out + (size_t)(a.height - 1 - j) * row, tmp.data() + j * row, row);
+  return RT_OK;
+}
+
+int rt_accum_get_info(const rt_accum* acc, rt_accum_info* info) {
+  if (!acc) return RT_ERR_ARG;
+  if (!info) return fail(acc->ctx, RT_ERR_ARG, "null info");
+  info->args = acc->args;
+  info->n_values = acc->per_fb;
+  info->scene_fp = acc->scene_fp;
+  return RT_OK;
+}
+
+float rt_accum_last_add_ms(const rt_accum* acc) {
+  float ms = 0.0f;
+  if (!acc || !acc->add_timed || hipEventElapsedTime(&ms, acc->ev[0], acc->ev[1]) != hipSuccess) return 0.0f;
+  return ms;
+}
+float rt_accum_last_image_ms(const rt_accum* acc) {
+  float ms = 0.0f;
+  if (!acc || !acc->image_timed || hipEventElapsedTime(&ms, acc->ev[2], acc->ev[3]) != hipSuccess) return 0.0f;
+  return ms;
+}
+
+int rt_accum_save(rt_accum* acc, void* blob, size_t cap, size_t* need) {
+  if (!acc) return RT_ERR_ARG;
+  rt_ctx* c = acc->ctx;
+  const size_t total = rtacc::kHeaderBytes + (size_t)acc->per_fb * sizeof(float);
+  if (need) *need = total;
+  if (!blob && cap == 0) return RT_OK;  // size query
+  if (!blob || cap < total) return fail(c, RT_ERR_ARG, "checkpoint buffer too small");
+  HIPCHK(c, hipSetDevice(c->device));
+  // the sums land in the blob's payload, then the header is packed around them
+  float* payload = reinterpret_cast<float*>(static_cast<unsigned char*>(blob) + rtacc::kHeaderBytes);
+  HIPCHK(c, hipMemcpyAsync(payload, acc->sums, (size_t)acc->per_fb * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  rt_accum_info info;
+  rt_accum_get_info(acc, &info);
+  if (rt_accum_blob_pack(&info, payload, blob, cap, nullptr)) return fail(c, RT_ERR_ARG, "pack checkpoint");
+  return RT_OK;
+}
+
+int rt_accum_load(rt_ctx* c, const void* blob, size_t n, int32_t chunk_fbs, rt_accum** out) {
+  if (!c) return RT_ERR_ARG;
+  if (!out) return fail(c, RT_ERR_ARG, "null accumulator pointer");
+  *out = nullptr;
+  rt_accum_info info;
+  if (rt_accum_blob_info(blob, n, &info)) return fail(c, RT_ERR_ARG, "malformed checkpoint");
+  if (!c->have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
+  if (info.scene_fp != c->scene_fp) return fail(c, RT_ERR_STATE, "checkpoint belongs to another scene");
+  if (info.args.fb_first > INT32_MAX - info.args.fb_count) return fail(c, RT_ERR_ARG, "malformed checkpoint");
+  rt_accum* acc = nullptr;
+  int rc = accum_new(c, &info.args, chunk_fbs, &acc);
+  if (rc) return rc;
+  if (acc->per_fb != info.n_values) rc = fail(c, RT_ERR_ARG, "malformed checkpoint");
+  const unsigned char* payload = static_cast<const unsigned char*>(blob) + rtacc::kHeaderBytes;
+  if (!rc && (hipMemcpyAsync(acc->sums, payload, (size_t)acc->per_fb * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+              hipStreamSynchronize(c->stream) != hipSuccess))
+    rc = fail(c, RT_ERR_HIP, "copy checkpoint sums to device");
+  if (rc) {
+    rt_accum_destroy(acc);
+    return rc;
+  }
+  acc->args.fb_count = info.args.fb_count;
+  *out = acc;
   return RT_OK;
 }
 
