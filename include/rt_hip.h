@@ -276,7 +276,32 @@ int rt_ctx_get_options(const rt_ctx* ctx, rt_ctx_options* opts);
 /* Rows of the image owned by a band tiling (ascending); returns the count. rows may be NULL. */
 int32_t rt_owned_rows(const rt_render_args* a, int32_t* rows);
 
-/* Copies the flattened scene to device memory owned by the context. */
+/* Checks a flattened scene on the host (no context, no HIP call): every index, count and type, the
+ * nesting rt_object_kind documents (which rules out cycles), the last BVH row's leaf_a (a primitive)
+ * and leaf_b (a primitive or -1), and the image records.  Beyond the struct comments above it holds
+ * a scene to this: a primitive is a leaf of at most one BVH, once, and is then not also named by a
+ * PRIM or LIST object; a checker's two textures are not checkers; perlin permutation entries are
+ * 0..255; a turbulence depth is 0..64; a triangle primitive's p[0] is a whole number below 2^19; an
+ * image with width <= 0 has no data (the reference's cyan), any other has height > 0, 1..4 bytes per
+ * pixel, and the three bytes pixel[0..2] of its last texel inside texels (texture.h:160-162 reads
+ * three bytes whatever bytes_per_pixel is: with 1 or 2 the row-major neighbours'); no sphere of a
+ * BVH (in the world, under a transform or as a medium's boundary; a moving one at both ends of the
+ * shutter) lies inside the camera's view cone more than 512 radii from the camera.  Returns RT_OK or
+ * RT_ERR_SCENE with the reason in msg (cap bytes, may be NULL).
+ *
+ * What is promised for a scene that passes: the reference's objects' pixels and segment counts, bit
+ * for bit, as far as sphere.h's float test resolves its spheres.  Its discriminant hb^2 - a cc carries a
+ * rounding error of the order of 2^-23 a L^2 (L = distance from the ray's origin to the centre), so the
+ * reference reports a BVH sphere "hit" by rays that pass up to sqrt(r^2 + 2^-23 L^2) from its centre,
+ * wherever its stored boxes let the test run; the culled search tests a sphere only where the ray
+ * enters the sphere's own box (padded by 2^-16), and the camera-ray tile lists where it enters the tile.
+ * Not promised, therefore: the outcome of a query whose ray starts more than 512 radii from a BVH sphere
+ * and passes it within that error zone but outside its box.  The rule above keeps camera rays out of that
+ * case; a bounce ray can get there (a path that leaves a far surface towards a small sphere), which no
+ * check at upload can rule out.  RT_FLAG_EXACT_TRAVERSAL has no such case. */
+int rt_scene_validate(const rt_scene_soa* scene, char* msg, size_t cap);
+
+/* Copies the flattened scene to device memory owned by the context; rt_scene_validate first. */
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_soa* scene);
 
 /* Per-slot XORWOW states curand_init(seed, slot, 0) for slot < width*height (render.h:84-92). */

@@ -24,6 +24,7 @@
 #include <thread>
 #include <vector>
 
+#include "../include/rt_hip.h"  // struct layouts of the flattened scene only (ref_scene_from_flat)
 #include "../raytracing_gpu_amd/csrc/rt_detmath.h"
 
 namespace oref {
@@ -281,6 +282,14 @@ struct Checker : Texture {  // texture.h:26-46
 struct Perlin {  // perlin.h:9-127
   V3 ranvec[256];
   int px[256], py[256], pz[256];
+  explicit Perlin(const rt_perlin& t) {  // the stored tables (ref_scene_from_flat)
+    for (int i = 0; i < 256; ++i) {
+      ranvec[i] = V3(t.ranvec[i][0], t.ranvec[i][1], t.ranvec[i][2]);
+      px[i] = t.perm_x[i] & 255;
+      py[i] = t.perm_y[i] & 255;
+      pz[i] = t.perm_z[i] & 255;
+    }
+  }
   explicit Perlin(Draw& g) {
     for (int i = 0; i < 256; ++i) ranvec[i] = unit(g.v3(-1.0f, 1.0f));
     perm(g, px);
@@ -327,6 +336,7 @@ struct NoiseTex : Texture {  // texture.h:49-62
   Perlin pn;
   float sc;
   NoiseTex(Draw& g, float s) : pn(g), sc(s) {}
+  NoiseTex(const Perlin& p, float s) : pn(p), sc(s) {}
   V3 value(float, float, const V3& p) const override {
     return V3(1, 1, 1) * 0.5f * (float)(1.0 + (double)pn.noise(sc * p));
   }
@@ -336,12 +346,14 @@ struct TurbTex : Texture {  // texture.h:65-77
   float sc;
   int depth;
   TurbTex(Draw& g, float s, int d = 7) : pn(g), sc(s), depth(d) {}
+  TurbTex(const Perlin& p, float s, int d) : pn(p), sc(s), depth(d) {}
   V3 value(float, float, const V3& p) const override { return V3(1, 1, 1) * pn.turb(sc * p, depth); }
 };
 struct MarbleTex : Texture {  // texture.h:80-91
   Perlin pn;
   float sc;
   MarbleTex(Draw& g, float s) : pn(g), sc(s) {}
+  MarbleTex(const Perlin& p, float s) : pn(p), sc(s) {}
   V3 value(float, float, const V3& p) const override {
     return V3(1, 1, 1) * 0.5f * (1.0f + rtm::det_sinf(sc * p.z + 10.0f * pn.turb(sc * p, 7)));
   }
@@ -353,6 +365,12 @@ struct ImageTex : Texture {  // texture.h:125-163 (decoded texels owned here)
   int w = 0, h = 0, bpp = 0;
   ImageTex(const uint8_t* d, int ww, int hh, int bb) : w(ww), h(hh), bpp(bb) {
     if (d && ww > 0 && hh > 0) data.assign(d, d + (size_t)ww * hh * bb);
+  }
+  // Texels inside a larger array (ref_scene_from_flat): value() reads pixel[0..2] whatever
+  // bytes_per_pixel is (texture.h:160-162), so with fewer than 3 bytes per pixel the bytes that
+  // follow belong to the next texels; nbytes covers them.
+  ImageTex(const uint8_t* d, int ww, int hh, int bb, size_t nbytes) : w(ww), h(hh), bpp(bb) {
+    if (d && ww > 0) data.assign(d, d + nbytes);
   }
   V3 value(float u, float v, const V3&) const override {
     if (data.empty()) return V3(0, 1, 1);  // texture.h:146-147
@@ -478,12 +496,15 @@ struct Sphere : Hittable {  // sphere.h:35-78
   }
 };
 struct MovingSphere : Hittable {  // moving_sphere.h:20-66
-  V3 c0, c1;
-  float t0, t1, rad;
+  V3 c0, d;        // d = center1 - center0
+  float t0, dt, rad;  // dt = time1 - time0
   const Material* m;
   MovingSphere(V3 a, V3 b, float ta, float tb, float r, const Material* mm)
-      : c0(a), c1(b), t0(ta), t1(tb), rad(r), m(mm) {}
-  V3 center(float t) const { return c0 + ((t - t0) / (t1 - t0)) * (c1 - c0); }
+      : c0(a), d(b - a), t0(ta), dt(tb - ta), rad(r), m(mm) {}
+  struct Stored {};  // the flattened record's d and dt as stored (c0 + d is not center1 in float)
+  MovingSphere(Stored, V3 a, V3 dd, float ta, float dtt, float r, const Material* mm)
+      : c0(a), d(dd), t0(ta), dt(dtt), rad(r), m(mm) {}
+  V3 center(float t) const { return c0 + ((t - t0) / dt) * d; }
   bool hit(const Ray& r, float tmin, float tmax, Rec& rec, Draw&) const override {
     const V3 oc = r.o - center(r.tm);
     const float a = r.d.len2();
@@ -513,9 +534,13 @@ struct MovingSphere : Hittable {  // moving_sphere.h:20-66
 struct Rect : Hittable {
   int ax;
   float a0, a1, b0, b1, k;
+  float wa, wb;  // a1 - a0, b1 - b0
   const Material* m;
   Rect(int axis, float p0, float p1, float q0, float q1, float kk, const Material* mm)
-      : ax(axis), a0(p0), a1(p1), b0(q0), b1(q1), k(kk), m(mm) {}
+      : ax(axis), a0(p0), a1(p1), b0(q0), b1(q1), k(kk), wa(p1 - p0), wb(q1 - q0), m(mm) {}
+  struct Stored {};  // the flattened record's extents as stored
+  Rect(Stored, int axis, float p0, float p1, float q0, float q1, float kk, float ea, float eb, const Material* mm)
+      : ax(axis), a0(p0), a1(p1), b0(q0), b1(q1), k(kk), wa(ea), wb(eb), m(mm) {}
   bool hit(const Ray& r, float tmin, float tmax, Rec& rec, Draw&) const override {
     // (a,b) = (x,y) for xy, (x,z) for xz, (y,z) for yz.
     const int ia = ax == 0 ? 1 : 0, ib = ax == 2 ? 1 : 2;
@@ -525,11 +550,11 @@ struct Rect : Hittable {
     const float b = r.o[ib] + t * r.d[ib];
     if (a < a0 || a > a1 || b < b0 || b > b1) return false;
     if (ax == 0) {  // yz_rect stores u from y and v from z
-      rec.v = (b - b0) / (b1 - b0);
-      rec.u = (a - a0) / (a1 - a0);
+      rec.v = (b - b0) / wb;
+      rec.u = (a - a0) / wa;
     } else {
-      rec.u = (a - a0) / (a1 - a0);
-      rec.v = (b - b0) / (b1 - b0);
+      rec.u = (a - a0) / wa;
+      rec.v = (b - b0) / wb;
     }
     rec.t = t;
     V3 nrm(0, 0, 0);
@@ -567,6 +592,13 @@ struct Triangle : Hittable {  // triangle.h:6-178
       n2 = n[2];
       vn = true;
     }
+  }
+  Triangle(const rt_triangle& t, const Material* mm)  // the flattened record's derived fields as stored
+      : p0(t.v0[0], t.v0[1], t.v0[2]), p1(t.v1[0], t.v1[1], t.v1[2]), p2(t.v2[0], t.v2[1], t.v2[2]),
+        e0(t.e0[0], t.e0[1], t.e0[2]), e1(t.e1[0], t.e1[1], t.e1[2]), n0(t.n0[0], t.n0[1], t.n0[2]),
+        n1(t.n1[0], t.n1[1], t.n1[2]), n2(t.n2[0], t.n2[1], t.n2[2]), d00(t.d00), d01(t.d01), d11(t.d11),
+        inv(t.inv_denom), vn(t.vertex_normals != 0), m(mm) {
+    for (int k = 0; k < 6; ++k) uv[k] = t.uv[k];
   }
   bool hit(const Ray& r, float tmin, float tmax, Rec& rec, Draw&) const override {  // :120-178
     const float eps = 0.0000001f;
@@ -693,6 +725,7 @@ struct RotateY : Hittable {
   float sn, cs;
   bool has;
   Box bb;
+  RotateY(const Hittable* c, float s, float co) : ch(c), sn(s), cs(co), has(false) {}  // stored sin / cos
   RotateY(const Hittable* c, float deg) : ch(c) {
     const float rad = deg * 3.1415927f / 180.0f;
     sn = rtm::det_sinf(rad);
@@ -741,6 +774,8 @@ struct Medium : Hittable {
   const Material* phase;
   float neg_inv;
   Medium(const Hittable* b, float dens, const Material* ph) : bnd(b), phase(ph), neg_inv(-1.0f / dens) {}
+  struct Stored {};  // the flattened record's -1/density as stored
+  Medium(Stored, const Hittable* b, float ni, const Material* ph) : bnd(b), phase(ph), neg_inv(ni) {}
   bool hit(const Ray& r, float tmin, float tmax, Rec& rec, Draw& g) const override {
     Rec r1, r2;
     if (!bnd->hit(r, -INFINITY, INFINITY, r1, g)) return false;
@@ -839,6 +874,25 @@ struct RefBvh : Hittable {
       bounds[k] = b0;
     }
     for (int k = last0 - 1; k >= 0; --k) bounds[k] = enclose(bounds[2 * k + 1], bounds[2 * k + 2]);
+  }
+  // Explicit nodes (ref_scene_from_flat): `r` inner levels in heap order, bounds[k] the stored boxes
+  // whatever they are, the last row's leaf_a / leaf_b indices into `prims`; num[k] from the leaves.
+  // The caller has checked r >= 1 and every last-row index.
+  RefBvh(const std::vector<const Hittable*>& prims, const rt_bvh_node* nd, int r) : objs(prims), rows(r) {
+    const int inner = (1 << rows) - 1, last0 = (1 << (rows - 1)) - 1;
+    num.assign(inner, 0);
+    leaf_a.assign(inner, -1);
+    leaf_b.assign(inner, -1);
+    bounds.resize(inner);
+    for (int k = 0; k < inner; ++k)
+      bounds[k] = Box{V3(nd[k].lo[0], nd[k].lo[1], nd[k].lo[2]), V3(nd[k].hi[0], nd[k].hi[1], nd[k].hi[2])};
+    for (int k = last0; k < inner; ++k) {
+      leaf_a[k] = nd[k].leaf_a;
+      leaf_b[k] = nd[k].leaf_b;
+      num[k] = leaf_b[k] >= 0 ? 2 : 1;
+    }
+    for (int k = last0 - 1; k >= 0; --k) num[k] = num[2 * k + 1] + num[2 * k + 2];
+    n = num[0];
   }
   // Depth-first, left child first; every box is tested against the caller's [tmin, tmax]; leaves
   // keep strictly smaller t (first hit wins ties).  Same visiting order as bvh.h:348-436.
@@ -1212,6 +1266,214 @@ static void build_coincident(ref_scene& s, Draw& g, bool step) {
   s.cam = Camera(V3(0.3f, 0.4f, -6.0f), V3(0, 0, 0), V3(0, 1, 0), 40, 16.0f / 9.0f, 0.1f, 6.0f, 0, 1);
 }
 
+// ---------------------------------------------------------------- a scene from the flat arrays
+// ref_scene_from_flat: the scene format of include/rt_hip.h (rt_scene_soa) as oracle objects.  The
+// flat scene is the definition: derived fields (a moving sphere's d and dt, a rect's extents, a
+// triangle's edges and dot products, a transform's sin / cos, a medium's -1/density, the camera's
+// vectors, a BVH's boxes) go in as stored, through the second constructors of the classes above, and
+// hit() keeps the reference's operation order.  Anything the format does not allow is a nonzero
+// status, never an abort: 2 = an index, count or type out of range, 3 = a nesting the format does
+// not document, 4 = a BVH record, 5 = an image record.
+struct FlatBuilder {
+  const rt_scene_soa& f;
+  ref_scene& s;
+  std::vector<const Texture*> tex;
+  std::vector<const Material*> mat;
+  std::vector<const Hittable*> prim;
+  std::vector<const Hittable*> obj;
+  int err = 0;
+
+  FlatBuilder(const rt_scene_soa& ff, ref_scene& ss) : f(ff), s(ss) {}
+  bool fail(int code) {
+    if (!err) err = code;
+    return false;
+  }
+
+  const Texture* leaf_texture(const rt_texture& t) {
+    const V3 col(t.color[0], t.color[1], t.color[2]);
+    switch (t.type) {
+      case RT_TEX_SOLID: return s.X<Solid>(col);
+      case RT_TEX_NOISE:
+      case RT_TEX_TURBULENT:
+      case RT_TEX_MARBLE: {
+        if (t.a < 0 || t.a >= f.n_perlins || !f.perlins) { fail(2); return nullptr; }
+        for (int i = 0; i < 256; ++i)  // an entry outside 0..255 would index past ranvec
+          if ((f.perlins[t.a].perm_x[i] | f.perlins[t.a].perm_y[i] | f.perlins[t.a].perm_z[i]) & ~255) {
+            fail(2);
+            return nullptr;
+          }
+        const Perlin pn(f.perlins[t.a]);
+        if (t.type == RT_TEX_NOISE) return s.X<NoiseTex>(pn, t.scale);
+        if (t.type == RT_TEX_MARBLE) return s.X<MarbleTex>(pn, t.scale);
+        if (t.b < 0 || t.b > 64) { fail(2); return nullptr; }
+        return s.X<TurbTex>(pn, t.scale, t.b);
+      }
+      case RT_TEX_IMAGE: {
+        if (t.a < 0 || t.a >= f.n_images || !f.images) { fail(2); return nullptr; }
+        const rt_image& im = f.images[t.a];
+        if (im.width <= 0) return s.X<ImageTex>(nullptr, 0, 0, 0);  // no data: cyan (texture.h:146-147)
+        const long long n = (long long)im.width * im.height * im.bytes_per_pixel;
+        // the last pixel's three bytes end at offset + n - bytes_per_pixel + 3
+        const long long reach = n + (im.bytes_per_pixel < 3 ? 3 - im.bytes_per_pixel : 0);
+        if (im.height <= 0 || im.bytes_per_pixel < 1 || im.bytes_per_pixel > 4 || im.offset < 0 || !f.texels ||
+            n >= (1LL << 31) || im.offset + reach > f.n_texels) {
+          fail(5);
+          return nullptr;
+        }
+        return s.X<ImageTex>(f.texels + im.offset, im.width, im.height, im.bytes_per_pixel, (size_t)reach);
+      }
+      default: fail(2); return nullptr;
+    }
+  }
+  bool textures() {
+    tex.assign((size_t)std::max(f.n_textures, 0), nullptr);
+    for (int k = 0; k < f.n_textures; ++k)
+      if (f.textures[k].type != RT_TEX_CHECKER && !(tex[k] = leaf_texture(f.textures[k]))) return false;
+    for (int k = 0; k < f.n_textures; ++k) {  // a checker's two textures are not checkers themselves
+      const rt_texture& t = f.textures[k];
+      if (t.type != RT_TEX_CHECKER) continue;
+      if (t.a < 0 || t.a >= f.n_textures || t.b < 0 || t.b >= f.n_textures) return fail(2);
+      if (f.textures[t.a].type == RT_TEX_CHECKER || f.textures[t.b].type == RT_TEX_CHECKER) return fail(3);
+      tex[k] = s.X<Checker>(tex[t.a], tex[t.b]);
+    }
+    return true;
+  }
+  bool materials() {
+    for (int k = 0; k < f.n_materials; ++k) {
+      const rt_material& m = f.materials[k];
+      const bool needs_tex = m.type != RT_MAT_DIELECTRIC;
+      if (m.type < RT_MAT_LAMBERTIAN || m.type > RT_MAT_ISOTROPIC) return fail(2);
+      if (needs_tex && (m.texture < 0 || m.texture >= f.n_textures)) return fail(2);
+      const Texture* t = needs_tex ? tex[m.texture] : nullptr;
+      switch (m.type) {
+        case RT_MAT_LAMBERTIAN: mat.push_back(s.M<Lambert>(t)); break;
+        case RT_MAT_METAL: mat.push_back(s.M<Metal>(t, m.param)); break;
+        case RT_MAT_DIELECTRIC: mat.push_back(s.M<Dielectric>(m.param)); break;
+        case RT_MAT_DIFFUSE_LIGHT: mat.push_back(s.M<Light>(t)); break;
+        default: mat.push_back(s.M<Isotropic>(t)); break;
+      }
+    }
+    return true;
+  }
+  bool prims() {
+    for (int k = 0; k < f.n_prims; ++k) {
+      const rt_prim& q = f.prims[k];
+      const float* p = q.p;
+      if (q.material < 0 || q.material >= f.n_materials) return fail(2);
+      const Material* m = mat[q.material];
+      switch (q.type) {
+        case RT_PRIM_SPHERE: prim.push_back(s.H<Sphere>(V3(p[0], p[1], p[2]), p[3], m)); break;
+        case RT_PRIM_MOVING_SPHERE:
+          prim.push_back(s.H<MovingSphere>(MovingSphere::Stored{}, V3(p[0], p[1], p[2]), V3(p[4], p[5], p[6]), p[7],
+                                           p[8], p[3], m));
+          break;
+        case RT_PRIM_RECT_XY:
+        case RT_PRIM_RECT_XZ:
+        case RT_PRIM_RECT_YZ: {
+          const int ax = q.type == RT_PRIM_RECT_XY ? 2 : (q.type == RT_PRIM_RECT_XZ ? 1 : 0);
+          prim.push_back(s.H<Rect>(Rect::Stored{}, ax, p[0], p[1], p[2], p[3], p[4], p[5], p[6], m));
+          break;
+        }
+        case RT_PRIM_TRIANGLE: {
+          if (!(p[0] >= 0.0f && p[0] < (float)f.n_triangles) || p[0] != (float)(int)p[0] || !f.triangles) return fail(2);
+          prim.push_back(s.H<Triangle>(f.triangles[(int)p[0]], m));
+          break;
+        }
+        case RT_PRIM_BOX: prim.push_back(s.H<BoxShape>(V3(p[0], p[1], p[2]), V3(p[3], p[4], p[5]), m)); break;
+        default: return fail(2);
+      }
+    }
+    return true;
+  }
+  // One object; `allowed` = bit mask of the kinds the parent may hold (rt_object_kind's comments).
+  const Hittable* object(int oi, unsigned allowed) {
+    if (oi < 0 || oi >= f.n_objects) { fail(2); return nullptr; }
+    const rt_object& o = f.objects[oi];
+    if (o.kind < RT_OBJ_PRIM || o.kind > RT_OBJ_MEDIUM) { fail(2); return nullptr; }
+    if (!((allowed >> o.kind) & 1u)) { fail(3); return nullptr; }
+    if (obj[oi]) return obj[oi];
+    const Hittable* h = nullptr;
+    const unsigned leafs = 1u << RT_OBJ_PRIM | 1u << RT_OBJ_LIST | 1u << RT_OBJ_BVH;
+    switch (o.kind) {
+      case RT_OBJ_PRIM:
+        if (o.a < 0 || o.a >= f.n_prims) { fail(2); return nullptr; }
+        h = prim[o.a];
+        break;
+      case RT_OBJ_LIST: {
+        if (o.a < 0 || o.b < 1 || (long long)o.a + o.b > f.n_prims) { fail(2); return nullptr; }
+        List* L = s.H<List>();
+        for (int k = 0; k < o.b; ++k) L->objs.push_back(prim[o.a + k]);
+        h = L;
+        break;
+      }
+      case RT_OBJ_BVH: {
+        if (o.b < 2 || o.b > 30 || o.a < 0 || (long long)o.a + (1LL << o.b) - 1 > f.n_nodes || !f.nodes) {
+          fail(4);
+          return nullptr;
+        }
+        const int inner = (1 << o.b) - 1, last0 = (1 << (o.b - 1)) - 1;
+        for (int k = last0; k < inner; ++k) {
+          const rt_bvh_node& nd = f.nodes[o.a + k];
+          if (nd.leaf_a < 0 || nd.leaf_a >= f.n_prims || nd.leaf_b < -1 || nd.leaf_b >= f.n_prims) {
+            fail(4);
+            return nullptr;
+          }
+        }
+        h = s.H<RefBvh>(prim, f.nodes + o.a, o.b);
+        break;
+      }
+      case RT_OBJ_XFORM: {
+        if (o.b < 0 || o.b > 3) { fail(2); return nullptr; }
+        const Hittable* c = object(o.a, leafs);
+        if (!c) return nullptr;
+        if (o.b & 2) c = s.H<RotateY>(c, o.f[3], o.f[4]);
+        if (o.b & 1) c = s.H<Translate>(c, V3(o.f[0], o.f[1], o.f[2]));
+        h = c;
+        break;
+      }
+      default: {  // RT_OBJ_MEDIUM
+        if (o.b < 0 || o.b >= f.n_materials) { fail(2); return nullptr; }
+        const Hittable* c = object(o.a, leafs | 1u << RT_OBJ_XFORM);
+        if (!c) return nullptr;
+        h = s.H<Medium>(Medium::Stored{}, c, o.f[0], mat[o.b]);
+        break;
+      }
+    }
+    obj[oi] = h;
+    return h;
+  }
+  bool build() {
+    if (f.n_world <= 0 || !f.world || f.n_objects <= 0 || !f.objects || f.n_materials <= 0 || !f.materials ||
+        f.n_prims < 0 || f.n_textures < 0 || f.n_triangles < 0 || f.n_nodes < 0 || f.n_perlins < 0 || f.n_images < 0 ||
+        f.n_texels < 0 || (f.n_prims > 0 && !f.prims) || (f.n_textures > 0 && !f.textures))
+      return fail(2);
+    if (!textures() || !materials() || !prims()) return false;
+    obj.assign((size_t)f.n_objects, nullptr);
+    List* W = s.H<List>();
+    for (int w = 0; w < f.n_world; ++w) {
+      const Hittable* h = object(f.world[w], 0x1fu);
+      if (!h) return false;
+      W->objs.push_back(h);
+    }
+    s.world = W;
+    const rt_camera& c = f.camera;
+    Camera& cam = s.cam;
+    cam.origin = V3(c.origin[0], c.origin[1], c.origin[2]);
+    cam.llc = V3(c.lower_left[0], c.lower_left[1], c.lower_left[2]);
+    cam.horiz = V3(c.horizontal[0], c.horizontal[1], c.horizontal[2]);
+    cam.vert = V3(c.vertical[0], c.vertical[1], c.vertical[2]);
+    cam.u = V3(c.u[0], c.u[1], c.u[2]);
+    cam.v = V3(c.v[0], c.v[1], c.v[2]);
+    cam.w = V3(c.w[0], c.w[1], c.w[2]);
+    cam.lens = c.lens_radius;
+    cam.t0 = c.time0;
+    cam.t1 = c.time1;
+    s.background = V3(f.background[0], f.background[1], f.background[2]);
+    s.aspect = f.aspect;
+    return true;
+  }
+};
+
 // ---------------------------------------------------------------- integrator (render.h:55-113)
 static V3 trace(const ref_scene& s, Ray r, Draw& g, int depth) {
   V3 att(1, 1, 1);
@@ -1294,6 +1556,16 @@ int ref_scene_create_ex(const char* name, int rtl, const ref_assets* a, ref_scen
   return 0;
 }
 int ref_scene_create(const char* name, int rtl, ref_scene** out) { return ref_scene_create_ex(name, rtl, nullptr, out); }
+int ref_scene_from_flat(const rt_scene_soa* flat, ref_scene** out) {
+  if (!flat || !out) return 1;
+  *out = nullptr;
+  std::unique_ptr<ref_scene> s(new ref_scene);
+  s->name = "flat";
+  FlatBuilder b(*flat, *s);
+  if (!b.build()) return b.err ? b.err : 1;
+  *out = s.release();
+  return 0;
+}
 void ref_scene_destroy(ref_scene* s) { delete s; }
 long long ref_capture_rays(float* buf, long long max_rays) {  // buf = NULL stops capturing
   const long long n = g_cap_n.exchange(0);

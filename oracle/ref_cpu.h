@@ -31,6 +31,11 @@ typedef struct ref_image { int width, height, bytes_per_pixel, pad; const uint8_
 typedef struct ref_mesh { int n_triangles, vertex_normals, image, pad; const float* data; } ref_mesh;
 typedef struct ref_assets { int n_images, n_meshes; const ref_image* images; const ref_mesh* meshes; } ref_assets;
 int ref_scene_create_ex(const char* name, int rtl, const ref_assets* assets, ref_scene** out);
+/* A scene from the flattened arrays of include/rt_hip.h (struct layouts only; no product code): the
+ * stored derived fields, camera vectors and BVH boxes are taken as they are.  The arrays are copied;
+ * 0 on success, nonzero (and *out = NULL) for anything the format does not allow -- never an abort. */
+struct rt_scene_soa;
+int ref_scene_from_flat(const struct rt_scene_soa* flat, ref_scene** out);
 void ref_scene_destroy(ref_scene* s);
 /* Capture world-query rays (8 floats: o, d, time, 0) into buf during later ref_render calls
  * (design experiments only); returns the number captured since the previous call. */

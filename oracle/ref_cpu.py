@@ -37,6 +37,7 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(LIB_PATH)
         L.ref_scene_create.argtypes = [ctypes.c_char_p, c_int, POINTER(c_void_p)]
         L.ref_scene_create_ex.argtypes = [ctypes.c_char_p, c_int, c_void_p, POINTER(c_void_p)]
+        L.ref_scene_from_flat.argtypes = [c_void_p, POINTER(c_void_p)]
         L.ref_scene_destroy.argtypes = [c_void_p]
         L.ref_scene_aspect.argtypes = [c_void_p]
         L.ref_scene_aspect.restype = c_float
@@ -93,6 +94,19 @@ class RefScene:
             rc = lib().ref_scene_create_ex(name.encode(), 1 if rtl else 0, ctypes.byref(a), ctypes.byref(self._h))
         if rc != 0:
             raise ValueError(f"unknown oracle scene {name!r} (or missing assets)")
+
+    @classmethod
+    def from_flat(cls, soa) -> "RefScene":
+        """The scene a flattened rt_scene_soa (include/rt_hip.h; a ctypes struct) describes: its stored
+        derived fields, camera vectors and BVH boxes as they are.  The arrays are copied.  ValueError
+        (with the oracle's status as .args[1]) for anything the format does not allow."""
+        self = cls.__new__(cls)
+        self.name = "flat"
+        self._h = c_void_p()
+        rc = lib().ref_scene_from_flat(ctypes.byref(soa), ctypes.byref(self._h))
+        if rc != 0:
+            raise ValueError("malformed flat scene", rc)
+        return self
 
     @property
     def aspect(self) -> float:

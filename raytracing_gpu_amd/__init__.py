@@ -44,7 +44,7 @@ RT_SCHED_PREVIOUS = 1
 RT_SCHED_SPLIT_REPLAY = 2
 RT_SCHED_PROBE = 4
 
-PRIM_SPHERE, PRIM_MOVING_SPHERE, PRIM_RECT_XY, PRIM_RECT_XZ, PRIM_RECT_YZ, PRIM_TRIANGLE = range(6)
+PRIM_SPHERE, PRIM_MOVING_SPHERE, PRIM_RECT_XY, PRIM_RECT_XZ, PRIM_RECT_YZ, PRIM_TRIANGLE, PRIM_BOX = range(7)
 OBJ_PRIM, OBJ_LIST, OBJ_BVH, OBJ_XFORM, OBJ_MEDIUM = range(5)
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT, MAT_ISOTROPIC = range(5)
 
@@ -149,6 +149,7 @@ ABI = {
     "rt_ctx_set_options": (c_int, [c_void_p, POINTER(rt_ctx_options)]),
     "rt_ctx_get_options": (c_int, [c_void_p, POINTER(rt_ctx_options)]),
     "rt_owned_rows": (c_int32, [POINTER(rt_render_args), POINTER(c_int32)]),
+    "rt_scene_validate": (c_int, [POINTER(rt_scene_soa), c_char_p, c_size_t]),
     "rt_scene_upload": (c_int, [c_void_p, POINTER(rt_scene_soa)]),
     "rt_render_init": (c_int, [c_void_p, c_int32, c_int32, c_uint64]),
     "rt_read_states": (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
@@ -307,6 +308,13 @@ class Scene:
 
 def scene(name: str) -> Scene:
     return Scene.builtin(name)
+
+
+def validate_scene(soa: rt_scene_soa) -> tuple[int, str]:
+    """rt_scene_validate on the host (no context, no GPU): (status, reason)."""
+    buf = ctypes.create_string_buffer(256)
+    rc = lib().rt_scene_validate(ctypes.byref(soa), buf, len(buf))
+    return int(rc), buf.value.decode()
 
 
 # ---------------------------------------------------------------- context (C ABI wrapper)

@@ -45,6 +45,7 @@
 #define RT_PRIM_FLAG_UV 0x100      // material needs sphere u,v (image texture)
 #define RT_PRIM_FLAG_UNIT_T 0x200  // moving sphere with time0 = 0, time1 - time0 = 1
 #define RT_PRIM_FLAG_XF 0x400      // world-tree leaf under a translate/rotate_y instance (F_WORLD)
+#define RT_PRIM_FLAG_OUT 0x800     // BVH leaf whose box sticks out of a stored box of its reference chain
 #define RT_WKEY_SHIFT 20           // world-tree tie key: (n_world - 1 - entry) << 20 | reference leaf rank
 
 // Scene feature mask: the render kernel is instantiated per feature set so that a scene pays
@@ -1009,8 +1010,12 @@ __device__ __forceinline__ bool chain_ok(const DScene& S, int base, int rows, co
     // the winner's own box than `bound` passes all of them: a sphere touches its box only at
     // six points, so the chain is rarely tested at all.  (Moving spheres: the box at the ray's
     // time lies inside the box over the shutter.  A negative radius inverts the box: no skip.)
+    // That holds for the reference's own boxes (unions of their children); a flattened scene may store
+    // any boxes, and a primitive that sticks out of one (RT_PRIM_FLAG_OUT, set at upload) takes the
+    // chain test below, where every position it sticks out of is in `must`.
+    // (the flag is kept in the compared word, so such a leaf matches neither type: no extra instruction)
     const PrimRec q = load_prim<F>(S, best_prim);
-    const int ty = prim_type(q);
+    const int ty = __float_as_int(q.c.z) & (RT_PRIM_TYPE_MASK | RT_PRIM_FLAG_OUT);
     if (ty == RT_PRIM_SPHERE || ((F & F_MOVING) != 0 && ty == RT_PRIM_MOVING_SPHERE)) {
       V c = mk(q.a.x, q.a.y, q.a.z);
       if constexpr ((F & F_MOVING) != 0)
@@ -3259,7 +3264,7 @@ bool tex_needs_uv(const rt_scene_soa* s, int ti) {
 // nodes[fb + 2i]: {lo0, child0}, {hi0, child1}, {lo1, -}, {hi1, -}; child >= 0 is a record,
 // child < 0 the primitive -child-1.  Also writes each primitive's reference leaf rank (its
 // position in the reference's depth-first left-first order) into prims[].p[9].
-// Returns the first node index of the new tree in `nodes`, or -1 if the reference tree is malformed.
+// Returns the first node index of the new tree in `nodes` (rt_scene_validate has checked the reference tree).
 struct SahBuilder {
   const std::vector<rth::Box>& box;
   std::vector<rt_bvh_node>& nodes;
@@ -3337,6 +3342,17 @@ struct SahBuilder {
   }
 };
 
+// Geometric box of a primitive over the shutter: bounding_box() (rth::prim_box) except for the
+// xz_rect, whose reference box spans z1 only (aarect.h:39, H4) and so does not bound the rect.
+rth::Box geom_box(const rt_prim& q, const rt_triangle* tris, float t0, float t1) {
+  rth::Box b = rth::prim_box(q, tris, t0, t1);
+  if ((q.type & 0xff) == RT_PRIM_RECT_XZ) {
+    b.lo[2] = std::fmin(q.p[2], q.p[3]);
+    b.hi[2] = std::fmax(q.p[2], q.p[3]);
+  }
+  return b;
+}
+
 int build_traversal_tree(const rt_scene_soa* s, int base, int rows, std::vector<rt_prim>& prims,
                          std::vector<rt_bvh_node>& nodes, std::vector<float2>& pmargin, std::vector<float4>& pvalid,
                          int* n_pairs, bool dedup) {
@@ -3347,17 +3363,17 @@ int build_traversal_tree(const rt_scene_soa* s, int base, int rows, std::vector<
     const int ids[2] = {nd.leaf_a, nd.leaf_b};
     for (int q = 0; q < 2; ++q) {
       if (ids[q] < 0) continue;
-      if (ids[q] >= s->n_prims) return -1;
       const int32_t rank = 2 * (k - last0) + q;
       memcpy(&prims[ids[q]].p[9], &rank, 4);
       members.push_back(ids[q]);
     }
   }
   const int n = (int)members.size();
-  if (n < 2 || n > (1 << rows)) return -1;
   const float t0 = s->camera.time0, t1 = s->camera.time1;
   std::vector<rth::Box> box(s->n_prims);
-  for (int id : members) box[id] = rth::prim_box(prims[id], s->triangles, t0 < t1 ? t0 : t1, t0 < t1 ? t1 : t0);
+  // (the geometric box: the reference's xz_rect box spans z1 only, H4, and where the stored boxes are not
+  // the reference's own a search tree built from it would miss the rect where the stored boxes show it)
+  for (int id : members) box[id] = geom_box(prims[id], s->triangles, t0 < t1 ? t0 : t1, t0 < t1 ? t1 : t0);
   // Safety margins of each primitive's reference chain: margin of chain position j = smallest
   // distance from the primitive's box (over the camera shutter) to the faces of its j-th
   // reference ancestor (position 0 = its last-row node).  Stored as {bitmask of positions with
@@ -3375,6 +3391,7 @@ int build_traversal_tree(const rt_scene_soa* s, int base, int rows, std::vector<
         for (int q = 0; q < 3; ++q) mm = std::min(mm, std::min(box[id].lo[q] - an.lo[q], an.hi[q] - box[id].hi[q]));
         if (!(mm >= 0.05f)) mask |= 1u << pos;
         else safe = std::min(safe, mm);
+        if (!(mm >= 0.0f)) prims[id].type |= RT_PRIM_FLAG_OUT;  // chain_ok's own-box shortcut does not apply
         if (a == 0) break;
       }
       float mbits;
@@ -3417,7 +3434,6 @@ int build_traversal_tree(const rt_scene_soa* s, int base, int rows, std::vector<
     for (int id : members) {
       if ((prims[id].type & 0xff) == RT_PRIM_TRIANGLE) {
         const int ti = (int)prims[id].p[0];
-        if (ti < 0 || ti >= s->n_triangles) return -1;
         const rt_triangle& t = s->triangles[ti];
         std::array<uint32_t, 9> key;
         memcpy(&key[0], t.v0, 12);
@@ -3893,16 +3909,6 @@ float4 box_sphere(const rth::Box& b) {
                      1e-6 * (std::fabs(cx) + std::fabs(cy) + std::fabs(cz)) + 1e-30;
   return make_float4((float)cx, (float)cy, (float)cz, (float)(rad * (1.0 + 1e-6)));
 }
-// Geometric box of a primitive over the shutter: bounding_box() (rth::prim_box) except for the
-// xz_rect, whose reference box spans z1 only (aarect.h:39, H4) and so does not bound the rect.
-rth::Box geom_box(const rt_prim& q, const rt_triangle* tris, float t0, float t1) {
-  rth::Box b = rth::prim_box(q, tris, t0, t1);
-  if ((q.type & 0xff) == RT_PRIM_RECT_XZ) {
-    b.lo[2] = std::fmin(q.p[2], q.p[3]);
-    b.hi[2] = std::fmax(q.p[2], q.p[3]);
-  }
-  return b;
-}
 // World-space box of a child-frame box cb under instance o (translate(rotate_y(child))).
 rth::Box xform_box(const rt_object& o, const rth::Box& cb) {
   // world = R^-1 (object) + offset, R^-1: x = c x' + s z', z = -s x' + c z' (hittable.h:112-143)
@@ -4166,23 +4172,12 @@ static bool build_qtree(const std::vector<rt_bvh_node>& nodes, int fb, int npair
 int rt_scene_upload(rt_ctx* c, const rt_scene_soa* s) {
   if (c) ++c->scene_gen;  // invalidates the row-cost schedule
   if (!c || !s) return RT_ERR_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (s->n_world <= 0 || !s->world || s->n_objects <= 0 || s->n_materials <= 0)
-    return fail(c, RT_ERR_SCENE, "empty scene");
-  for (int k = 0; k < s->n_world; ++k)
-    if (s->world[k] < 0 || s->world[k] >= s->n_objects) return fail(c, RT_ERR_SCENE, "world index out of range");
-  for (int k = 0; k < s->n_objects; ++k) {
-    const rt_object& o = s->objects[k];
-    if (o.kind == RT_OBJ_BVH && (o.b < 2 || o.b > 30 || o.a < 0 || o.a + (1 << o.b) - 1 > s->n_nodes))
-      return fail(c, RT_ERR_SCENE, "bvh out of range");
-    if ((o.kind == RT_OBJ_PRIM || o.kind == RT_OBJ_LIST) && (o.a < 0 || o.a + (o.kind == RT_OBJ_LIST ? o.b : 1) > s->n_prims))
-      return fail(c, RT_ERR_SCENE, "prim index out of range");
-    if ((o.kind == RT_OBJ_XFORM || o.kind == RT_OBJ_MEDIUM) && (o.a < 0 || o.a >= s->n_objects))
-      return fail(c, RT_ERR_SCENE, "child object out of range");
+  {  // every index, count, type and nesting, before anything reaches the device (rt_validate.cpp)
+    char why[160];
+    const int vrc = rt_scene_validate(s, why, sizeof(why));
+    if (vrc != RT_OK) return fail(c, vrc, why);
   }
-  for (int k = 0; k < s->n_prims; ++k)
-    if (s->prims[k].material < 0 || s->prims[k].material >= s->n_materials)
-      return fail(c, RT_ERR_SCENE, "prim material out of range");
+  HIPCHK(c, hipSetDevice(c->device));
   free_scene(c);
   // the fingerprint accumulator checkpoints are tied to (byte-serial FNV-1a over the caller's arrays,
   // which the context does not keep: 0.6 GB/s on the host)
@@ -4210,7 +4205,6 @@ int rt_scene_upload(rt_ctx* c, const rt_scene_soa* s) {
     if (o.kind == RT_OBJ_BVH) {
       const int fast = build_traversal_tree(s, o.a, o.b, prims, nodes, pmargin, pvalid, &tree_pairs[k],
                                             c->opt.dedup_triangles != 0);
-      if (fast < 0) return fail(c, RT_ERR_SCENE, "malformed reference bvh");
       o.c = fast;
     }
   }
@@ -4220,7 +4214,6 @@ int rt_scene_upload(rt_ctx* c, const rt_scene_soa* s) {
   for (rt_prim& p : prims) {
     if ((p.type & 0xff) != RT_PRIM_TRIANGLE) continue;
     const int ti = (int)p.p[0];
-    if (ti < 0 || ti >= s->n_triangles || ti >= (1 << 19)) return fail(c, RT_ERR_SCENE, "triangle index out of range");
     const rt_triangle& t = s->triangles[ti];
     for (int k = 0; k < 3; ++k) {
       p.p[k] = t.v0[k];
@@ -4273,17 +4266,22 @@ int rt_scene_upload(rt_ctx* c, const rt_scene_soa* s) {
   for (rt_image& im : dimages) {
     if (im.width <= 0) continue;  // no data: the cyan fallback (texture.h:146-147)
     const long long n = (long long)im.width * im.height * im.bytes_per_pixel;
-    if (im.height <= 0 || im.bytes_per_pixel < 1 || im.bytes_per_pixel > 4 || im.offset < 0 || im.offset + n > s->n_texels)
-      return fail(c, RT_ERR_SCENE, "image texels out of range");
-    if (dtexels.size() + ((size_t)n * 2) >= (size_t)1 << 31) return fail(c, RT_ERR_SCENE, "textures too large");
+    if (dtexels.size() + ((size_t)n * (im.bytes_per_pixel < 3 ? 6 : 2)) >= (size_t)1 << 31)
+      return fail(c, RT_ERR_SCENE, "textures too large");
     const uint8_t* src = s->texels + im.offset;
-    const int bpp = im.bytes_per_pixel, tpr = (im.width + 7) >> 3, tpc = (im.height + 7) >> 3;
+    // A texel's value is pixel[0..2] whatever bytes_per_pixel is (texture.h:160-162): with 1 or 2
+    // bytes per pixel the second and third byte are the row-major neighbours' (rt_scene_validate keeps
+    // them inside texels), which are not the tiled copy's neighbours, so such an image is widened to
+    // 3 bytes per texel here, each texel carrying the three bytes the reference reads.
+    const int sbpp = im.bytes_per_pixel, bpp = sbpp < 3 ? 3 : sbpp;
+    const int tpr = (im.width + 7) >> 3, tpc = (im.height + 7) >> 3;
     const size_t base = dtexels.size();
     dtexels.resize(base + (size_t)tpr * tpc * 64 * bpp, 0);
     for (int j = 0; j < im.height; ++j)
       for (int i = 0; i < im.width; ++i)
         memcpy(&dtexels[base + (((size_t)((j >> 3) * tpr + (i >> 3)) << 6) + ((j & 7) << 3) + (i & 7)) * bpp],
-               src + ((size_t)j * im.width + i) * bpp, (size_t)bpp);
+               src + ((size_t)j * im.width + i) * sbpp, (size_t)bpp);
+    im.bytes_per_pixel = bpp;
     im.offset = (int32_t)base;
   }
   if ((rc = upload(c, dimages.data(), dimages.size(), &d.images))) return rc;
