@@ -16,11 +16,18 @@
 //     --checkpoint FILE     one GPU: save the accumulator to FILE after every step (one step of NO_FB
 //                           frame buffers without --progressive) and, when FILE exists, continue
 //                           from it up to NO_FB (prints a JSON line with "resumed_from")
+//     --until-noise T       with --progressive: attach a noise monitor (rt_noise) and stop once at most
+//     --noisy-fraction F    floor(F x pixels) pixels (default F = 0.01) have a noise estimate above T
+//                           8-bit levels, measured after every step from 2 frame buffers on; NO_FB stays
+//                           the upper limit.  Each step's JSON line gains "noise_max" and "pixels_above",
+//                           a last line carries "stopped_at".  With --checkpoint FILE the monitor is
+//                           saved to FILE.noise before FILE, and resuming needs it
 //
 // Writes OUT.ppm (binary P6, top row first) and one JSON line per draw on stdout.  Files written
 // more than once go to a temporary name first and are renamed into place.
 #include <chrono>
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -86,8 +93,10 @@ bool read_file(const char* path, std::vector<unsigned char>& out) {
 // draw() through an accumulator: `step` frame buffers at a time, OUT.ppm and the checkpoint
 // rewritten after each step.
 int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int step, const char* ckpt,
-                     const char* out, std::vector<uint8_t>& png) {
+                     const char* out, std::vector<uint8_t>& png, bool until_noise, float noise_t, double noisy_fraction) {
   rt_accum* acc = nullptr;
+  rt_noise* mon = nullptr;
+  const std::string side = std::string(ckpt ? ckpt : "") + ".noise";
   std::vector<unsigned char> blob;
   if (ckpt && read_file(ckpt, blob)) {
     if (rt_accum_load(ctx, blob.data(), blob.size(), step, &acc)) return die("rt_accum_load", rt_last_error(ctx));
@@ -98,23 +107,45 @@ int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int
         b.max_depth != a.max_depth || b.cam_mode != a.cam_mode || b.band_rows != a.band_rows ||
         b.band_first != a.band_first || b.band_stride != a.band_stride || b.seed != a.seed || b.fb_count > a.fb_count)
       return die("checkpoint", "belongs to a draw with other settings");
+    if (until_noise) {  // the statistics cover every frame buffer or the draw does not continue
+      std::vector<unsigned char> nb;
+      if (!read_file(side.c_str(), nb)) return die("--until-noise: the checkpoint has no side file", side.c_str());
+      if (rt_noise_load(acc, nb.data(), nb.size(), &mon)) return die("rt_noise_load", rt_last_error(ctx));
+    }
     printf("{\"resumed_from\": %d, \"checkpoint\": \"%s\"}\n", b.fb_count, ckpt);
     fflush(stdout);
   } else if (rt_accum_create(ctx, &a, step, &acc)) {
     return die("rt_accum_create", rt_last_error(ctx));
+  } else if (until_noise && rt_noise_create(acc, &mon)) {
+    return die("rt_noise_create", rt_last_error(ctx));
   }
   char head[64];
   snprintf(head, sizeof(head), "P6\n%d %d\n255\n", a.width, a.height);
   rt_accum_info i = {};
   rt_accum_get_info(acc, &i);
-  for (bool first = true; first || i.args.fb_count < a.fb_count; first = false) {
+  const long long pixels = (long long)a.width * a.height;
+  auto converged = [&](const rt_noise_report& r) { return r.pixels_above <= (long long)std::floor(noisy_fraction * (double)pixels); };
+  bool stop = false;
+  if (mon && i.args.fb_count >= 2) {  // resumed: a draw that had converged stays stopped
+    rt_noise_report r = {};
+    if (rt_noise_measure(mon, noise_t, &r, nullptr, nullptr)) return die("rt_noise_measure", rt_last_error(ctx));
+    stop = converged(r);
+  }
+  for (bool first = true; first || (i.args.fb_count < a.fb_count && !stop); first = false) {
     const auto t0 = std::chrono::steady_clock::now();
     rt_counters c = {};
-    const int n = std::min(step, a.fb_count - i.args.fb_count);
+    const int n = stop ? 0 : std::min(step, a.fb_count - i.args.fb_count);
     if (n > 0 && rt_accum_add(acc, n, &c)) return die("rt_accum_add", rt_last_error(ctx));
     if (rt_accum_image(acc, png.data(), 1)) return die("rt_accum_image", rt_last_error(ctx));
     rt_accum_get_info(acc, &i);
     if (!write_file(out, head, png.data(), png.size())) return die("write", out);
+    if (ckpt && n > 0 && mon) {  // before the checkpoint: a checkpoint never lacks its side file
+      size_t need = 0;
+      rt_noise_save(mon, nullptr, 0, &need);
+      blob.resize(need);
+      if (rt_noise_save(mon, blob.data(), blob.size(), nullptr)) return die("rt_noise_save", rt_last_error(ctx));
+      if (!write_file(side, "", blob.data(), blob.size())) return die("write", side.c_str());
+    }
     if (ckpt && n > 0) {
       size_t need = 0;
       rt_accum_save(acc, nullptr, 0, &need);
@@ -123,11 +154,25 @@ int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int
       if (!write_file(ckpt, "", blob.data(), blob.size())) return die("write", ckpt);
     }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    rt_noise_report rep = {};
+    const bool measured = mon && i.args.fb_count >= 2;
+    if (measured) {
+      if (rt_noise_measure(mon, noise_t, &rep, nullptr, nullptr)) return die("rt_noise_measure", rt_last_error(ctx));
+      stop = converged(rep);
+    }
     printf("{\"fbs_done\": %d, \"scene\": \"%s\", \"width\": %d, \"height\": %d, \"wall_ms\": %.3f, "
-           "\"segments\": %llu, \"samples\": %llu}\n",
+           "\"segments\": %llu, \"samples\": %llu",
            i.args.fb_count, name, a.width, a.height, ms, (unsigned long long)c.segments, (unsigned long long)c.samples);
+    if (measured) printf(", \"noise_max\": %.9g, \"pixels_above\": %lld", rep.max_noise, (long long)rep.pixels_above);
+    printf("}\n");
     fflush(stdout);
   }
+  if (until_noise) {
+    printf("{\"stopped_at\": %d, \"converged\": %s, \"until_noise\": %.9g, \"noisy_fraction\": %.9g}\n", i.args.fb_count,
+           stop ? "true" : "false", noise_t, noisy_fraction);
+    fflush(stdout);
+  }
+  if (mon) rt_noise_destroy(mon);
   rt_accum_destroy(acc);
   return 0;
 }
@@ -137,7 +182,8 @@ int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int
 int main(int argc, char** argv) {
   if (argc < 6) {
     fprintf(stderr, "usage: rt_main SCENE WIDTH SPP_PER_FB NO_FB OUT.ppm [--devices 0,1] [--gather rccl|host] "
-                    "[--band-rows B] [--repeat K] [--depth D] [--obj PATH] [--tex PATH] [--progressive K] [--checkpoint FILE]\n");
+                    "[--band-rows B] [--repeat K] [--depth D] [--obj PATH] [--tex PATH] [--progressive K] [--checkpoint FILE] "
+                    "[--until-noise T [--noisy-fraction F]]\n");
     return 2;
   }
   const char* name = argv[1];
@@ -150,6 +196,9 @@ int main(int argc, char** argv) {
   int gather = RT_GATHER_RCCL, band_rows = 4, repeat = 1;
   const char *obj_path = nullptr, *tex_path = nullptr, *ckpt_path = nullptr;
   int progressive = 0;
+  bool until_noise = false, have_fraction = false;
+  float noise_t = 0.0f;
+  double noisy_fraction = 0.01;
   for (int k = 6; k < argc; ++k) {
     const std::string a = argv[k];
     const char* v = k + 1 < argc ? argv[k + 1] : "";
@@ -162,8 +211,14 @@ int main(int argc, char** argv) {
     else if (a == "--tex") tex_path = v, ++k;
     else if (a == "--progressive") progressive = atoi(v), ++k;
     else if (a == "--checkpoint") ckpt_path = v, ++k;
+    else if (a == "--until-noise") until_noise = true, noise_t = (float)atof(v), ++k;
+    else if (a == "--noisy-fraction") have_fraction = true, noisy_fraction = atof(v), ++k;
     else return die("unknown option", argv[k]);
   }
+
+  if ((until_noise || have_fraction) && progressive <= 0) return die("--until-noise / --noisy-fraction", "need --progressive K");
+  if (have_fraction && !until_noise) return die("--noisy-fraction", "needs --until-noise T");
+  if (until_noise && s.no_fb > 32768) return die("--until-noise", "a noise monitor accepts at most 32768 frame buffers");
 
   // ---- scene: the reference's `door_scene curr_scene;` etc. (main.cu:17-18) as the host library
   rt_scene_host* scene = nullptr;
@@ -224,7 +279,8 @@ int main(int argc, char** argv) {
   if (progressive != 0 || ckpt_path) {
     if (!ctx) return die("--progressive / --checkpoint", "one GPU only (no --devices)");
     if (progressive < 0 || a.fb_count < 1) return die("--progressive", "K and NO_FB must be at least 1");
-    const int rc = draw_progressive(ctx, name, a, progressive > 0 ? progressive : a.fb_count, ckpt_path, out, png);
+    const int rc = draw_progressive(ctx, name, a, progressive > 0 ? progressive : a.fb_count, ckpt_path, out, png,
+                                      until_noise, noise_t, noisy_fraction);
     rt_ctx_destroy(ctx);
     rt_scene_free(scene);
     return rc;

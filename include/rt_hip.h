@@ -397,6 +397,82 @@ int rt_accum_blob_info(const void* blob, size_t n, rt_accum_info* info);
 int rt_accum_blob_image(const void* blob, size_t n, uint8_t* out);
 int rt_accum_blob_pack(const rt_accum_info* info, const float* sums, void* blob, size_t cap, size_t* need);
 
+/* ------------------------------------------------------------------ noise monitor */
+/* Is the image finished?  Every frame buffer is an independent estimate of the picture, and
+ * average_images only sees its 8-bit quantisation, so the spread of c^2 across frame buffers, per
+ * pixel, is the noise of the final image.  A monitor rides on an accumulator and keeps the first two
+ * moments of c^2 as integers: exact, independent of order and grouping, identical across chunks,
+ * checkpoints and band shares.  It changes no pixel; an accumulator without one launches the kernels
+ * it launched before.
+ *
+ * For every accumulator value k (a channel of an owned pixel), over the n frame buffers folded in
+ * since the monitor was created, with c = quant(fb[f][k]) as in accum_add_kernel:
+ *
+ *   S1[k] = sum of c^2   (u32)
+ *   S2[k] = sum of c^4   (u64)
+ *
+ * A monitor accepts at most 32 768 frame buffers; a fold that would exceed this returns RT_ERR_ARG
+ * before anything is rendered or written.  With that cap every quantity below fits in unsigned 64-bit
+ * arithmetic: c^2 <= 65 025 and c^4 < 2^32, so n S2 <= 4.6e18 and S1^2 <= 4.6e18, and the
+ * three-channel sum is <= 1.4e19 < 2^64.
+ *
+ * Per pixel, over its three channels j:
+ *
+ *   D = sum_j (n S2_j - S1_j^2)    (u64; each term is >= 0 by Cauchy-Schwarz)
+ *   S = sum_j S1_j                 (u64)
+ *
+ * In double, with operations in exactly this order:
+ *
+ *   a     = (double)D / (3.0 * n * n * (n - 1) * 4228250625.0)   mean over channels of var(x)/n, x = c^2/65025
+ *   m     = (double)S / (3.0 * n * 65025.0);  if (m < 0x1p-16) m = 0x1p-16;
+ *   noise = (float)(128.0 * sqrt(a / m))
+ *
+ * noise is the standard error of the pixel in 8-bit output levels: the output level is 256 sqrt(m),
+ * so an error dm moves it by 128 dm / sqrt(m).  It is 0 for a pixel whose frame buffers all agree,
+ * and it needs n >= 2 (otherwise RT_ERR_STATE).
+ *
+ * Tiles are 16 x 16 pixels over (owned-row index, column), row-major (tile ty * tiles_x + tx); edge
+ * tiles are partial.  For a band tiling the row index is the position in the list of rt_owned_rows. */
+typedef struct rt_noise rt_noise;
+typedef struct rt_noise_report {
+  int32_t fbs, tiles_x, tiles_y, pad;
+  int64_t pixels, pixels_above;     /* owned pixels; those with noise > threshold */
+  float threshold, max_noise;
+} rt_noise_report;
+
+/* Attaches a monitor to an accumulator that has folded in no frame buffer and has no monitor
+ * (RT_ERR_STATE otherwise: a monitor sees every frame buffer or none).  While it is attached every
+ * fold also updates it (one fused kernel instead of accum_add_kernel).  Destroying the accumulator
+ * first detaches the monitor: its calls then return RT_ERR_STATE, and the destroy call still frees it.
+ * 12 bytes of device memory per accumulator value. */
+int rt_noise_create(rt_accum* acc, rt_noise** out);
+/* Measures the frame buffers so far: the report, and per tile the maximum noise and the number of
+ * pixels with noise > threshold (host arrays of tiles_x x tiles_y, either may be NULL; rep may be
+ * NULL).  No float is ever summed, so every output is independent of reduction order. */
+int rt_noise_measure(rt_noise* nm, float threshold, rt_noise_report* rep, float* tile_max, int32_t* tile_above);
+/* The per-pixel noise, [owned_rows][width] floats, device or host pointer. */
+int rt_noise_map(rt_noise* nm, float* out);
+/* Side file of a checkpoint (little-endian): the accumulator blob's 96-byte header with magic
+ * "RTNOISE1", version 1 and fb_count = frame buffers measured; then n_values u64 S2, then n_values
+ * u32 S1.  Save follows the size-query convention of the accumulator's.  Load attaches a monitor in
+ * the saved state: RT_ERR_STATE unless every header field equals the accumulator's rt_accum_info
+ * (fb_first, fb_count and the scene fingerprint included) and the accumulator has no monitor;
+ * RT_ERR_ARG for a malformed blob. */
+int rt_noise_save(rt_noise* nm, void* blob, size_t cap, size_t* need);
+int rt_noise_load(rt_accum* acc, const void* blob, size_t n, rt_noise** out);
+/* Device time in ms of the last measure or map kernel (the reduction to the image totals included);
+ * 0 before one. */
+float rt_noise_last_measure_ms(const rt_noise* nm);
+int rt_noise_destroy(rt_noise* nm);
+/* Host only (no context, no GPU; csrc/rt_noise_blob.cpp): validate a side file and fill info
+ * (RT_ERR_ARG for truncation, another magic or version, a size that does not match n_values and the
+ * tiling, a checksum mismatch, fb_count > 32768); build one from an info and its moments; measure
+ * one as the device does (every output may be NULL; map is [owned_rows][width]). */
+int rt_noise_blob_info(const void* blob, size_t n, rt_accum_info* info);
+int rt_noise_blob_pack(const rt_accum_info* info, const uint32_t* s1, const uint64_t* s2, void* blob, size_t cap, size_t* need);
+int rt_noise_blob_measure(const void* blob, size_t n, float threshold, rt_noise_report* rep,
+                          float* tile_max, int32_t* tile_above, float* map);
+
 /* ------------------------------------------------------------------ host scene library */
 /* Builds one of the reference scenes (scenes.h) on the host: "basic", "first", "big1" (alias
  * "random"), "two_spheres", "two_perlin", "cornell", "cornell_smoke", "triangle", "triangles",

@@ -9,7 +9,9 @@ Host mirror of the reference's interface for that path (names and argument meani
     quantise + square-average); returns the PNG raster instead of writing ./image.png
   * ``draw_progressive(scene, settings, every=..., on_image=..., checkpoint=...)`` — the same draw
     cut after any frame buffer (the reference keeps tmp/<id>.ppm per fb, render.h:152-162):
-    previews, stop and resume through ``Context.accumulator`` / ``Accumulator`` / ``read_checkpoint``
+    previews, stop and resume through ``Context.accumulator`` / ``Accumulator`` / ``read_checkpoint``;
+    ``until_noise=`` stops the draw once the per-pixel noise estimate of ``Accumulator.noise_monitor``
+    (``NoiseMonitor``, ``read_noise``) says the 8-bit image has converged
   * ``Context.render_init / render / resolve`` — the kernels render_init (render.h:84-92) and
     render (render.h:94-113) behind the C ABI of include/rt_hip.h
 
@@ -19,6 +21,7 @@ if the library is missing or the device call fails, the call raises.
 from __future__ import annotations
 
 import ctypes
+import math
 import sys
 import os
 from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint64, c_void_p
@@ -140,6 +143,20 @@ class rt_accum_info(ctypes.Structure):
         return d
 
 
+class rt_noise_report(ctypes.Structure):
+    """include/rt_hip.h rt_noise_report."""
+    _fields_ = [("fbs", c_int32), ("tiles_x", c_int32), ("tiles_y", c_int32), ("pad", c_int32),
+                ("pixels", c_int64), ("pixels_above", c_int64), ("threshold", c_float), ("max_noise", c_float)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k in ("fbs", "tiles_x", "tiles_y", "pixels", "pixels_above")}
+        d["threshold"] = float(self.threshold)
+        d["max_noise"] = float(self.max_noise)
+        return d
+
+
+NOISE_MAX_FBS = 32768  # frame buffers a noise monitor accepts (include/rt_hip.h)
+
 # Every entry point of include/rt_hip.h: name -> (restype, argtypes)
 ABI = {
     "rt_ctx_create": (c_int, [c_int, POINTER(c_void_p)]),
@@ -174,6 +191,16 @@ ABI = {
     "rt_accum_blob_info": (c_int, [c_void_p, c_size_t, POINTER(rt_accum_info)]),
     "rt_accum_blob_image": (c_int, [c_void_p, c_size_t, c_void_p]),
     "rt_accum_blob_pack": (c_int, [POINTER(rt_accum_info), c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]),
+    "rt_noise_create": (c_int, [c_void_p, POINTER(c_void_p)]),
+    "rt_noise_measure": (c_int, [c_void_p, c_float, POINTER(rt_noise_report), c_void_p, c_void_p]),
+    "rt_noise_map": (c_int, [c_void_p, c_void_p]),
+    "rt_noise_save": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]),
+    "rt_noise_load": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_void_p)]),
+    "rt_noise_last_measure_ms": (c_float, [c_void_p]),
+    "rt_noise_destroy": (c_int, [c_void_p]),
+    "rt_noise_blob_info": (c_int, [c_void_p, c_size_t, POINTER(rt_accum_info)]),
+    "rt_noise_blob_pack": (c_int, [POINTER(rt_accum_info), c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]),
+    "rt_noise_blob_measure": (c_int, [c_void_p, c_size_t, c_float, POINTER(rt_noise_report), c_void_p, c_void_p, c_void_p]),
     "rt_scene_build": (c_int, [c_char_p, POINTER(c_void_p)]),
     "rt_scene_build_ex": (c_int, [c_char_p, c_void_p, POINTER(c_void_p)]),
     "rt_obj_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
@@ -546,7 +573,19 @@ class Accumulator:
             f.write(self.blob())
         os.replace(tmp, path)
 
+    def noise_monitor(self) -> "NoiseMonitor":
+        """Attach a noise monitor (rt_noise_create): only to an accumulator that has folded in no
+        frame buffer and has none yet (RT_ERR_STATE otherwise).  From here on every add() / add_fbs()
+        also updates its integer moments; the image and the checkpoint stay byte-identical."""
+        h = c_void_p()
+        self.ctx._check(lib().rt_noise_create(self._h, ctypes.byref(h)), "rt_noise_create")
+        return NoiseMonitor(self, h)
+
     def close(self) -> None:
+        """Destroys the accumulator; its noise monitor, if any, is closed first."""
+        mon = getattr(self, "_monitor", None)
+        if mon is not None:
+            mon.close()
         if getattr(self, "_h", None):
             if getattr(self.ctx, "_c", None):
                 lib().rt_accum_destroy(self._h)
@@ -557,6 +596,109 @@ class Accumulator:
             self.close()
         except Exception:
             pass
+
+
+class NoiseMonitor:
+    """rt_noise of include/rt_hip.h: per accumulator value the exact integer moments of c^2 over the
+    frame buffers folded in, from which measure() / map() give the standard error of every pixel in
+    8-bit output levels.  Integer sums: the same whatever the chunking, checkpointing or band tiling."""
+
+    def __init__(self, acc: Accumulator, handle: c_void_p):
+        self.acc = acc
+        self._h = handle
+        acc._monitor = self
+        i = acc.info()
+        self._rows, self._width = i["n_values"] // (3 * i["width"]), i["width"]
+
+    @classmethod
+    def load(cls, acc: Accumulator, path: str) -> "NoiseMonitor":
+        """Attach the monitor saved at path to acc: RtError with status RT_ERR_STATE unless the file's
+        header equals acc.info() in every field (frame buffers done and scene included), RT_ERR_ARG
+        for a malformed file."""
+        with open(path, "rb") as f:
+            blob = f.read()
+        h = c_void_p()
+        acc.ctx._check(lib().rt_noise_load(acc._h, blob, len(blob), ctypes.byref(h)), "rt_noise_load")
+        return cls(acc, h)
+
+    def _check(self, rc: int, what: str) -> None:
+        self.acc.ctx._check(rc, what)
+
+    def measure(self, threshold: float) -> tuple[dict, np.ndarray, np.ndarray]:
+        """(report, tile_max, tile_above): the report as a dict (fbs, tiles_x, tiles_y, pixels,
+        pixels_above = pixels with noise > threshold, threshold, max_noise) and the per-tile maximum
+        (float32) and count (int32) as (tiles_y, tiles_x) arrays over 16 x 16 pixel tiles.  Needs two
+        frame buffers (RT_ERR_STATE before)."""
+        ty, tx = (self._rows + 15) // 16, (self._width + 15) // 16
+        tile_max, tile_above = np.zeros((ty, tx), np.float32), np.zeros((ty, tx), np.int32)
+        rep = rt_noise_report()
+        self._check(lib().rt_noise_measure(self._h, threshold, ctypes.byref(rep), tile_max.ctypes.data,
+                                           tile_above.ctypes.data), "rt_noise_measure")
+        return rep.as_dict(), tile_max, tile_above
+
+    def map(self) -> np.ndarray:
+        """The noise of every owned pixel, (owned_rows, width) float32, owned rows ascending."""
+        out = np.zeros((self._rows, self._width), np.float32)
+        self._check(lib().rt_noise_map(self._h, out.ctypes.data), "rt_noise_map")
+        return out
+
+    def map_into(self, out_ptr: int) -> None:
+        """map() into caller memory (a device or host address)."""
+        self.acc.ctx._after_torch()
+        self._check(lib().rt_noise_map(self._h, c_void_p(out_ptr)), "rt_noise_map")
+
+    def last_measure_ms(self) -> float:
+        """Device time of the last measure() / map() kernel."""
+        return float(lib().rt_noise_last_measure_ms(self._h))
+
+    def blob(self) -> bytes:
+        need = c_size_t()
+        self._check(lib().rt_noise_save(self._h, None, 0, ctypes.byref(need)), "rt_noise_save")
+        buf = ctypes.create_string_buffer(need.value)
+        self._check(lib().rt_noise_save(self._h, buf, need.value, None), "rt_noise_save")
+        return buf.raw
+
+    def save(self, path: str) -> None:
+        """Write the monitor's side file to path: to a temporary name beside it first, then renamed."""
+        tmp = f"{path}.tmp{os.getpid()}"
+        with open(tmp, "wb") as f:
+            f.write(self.blob())
+        os.replace(tmp, path)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().rt_noise_destroy(self._h)
+            self._h = None
+        if getattr(self.acc, "_monitor", None) is self:
+            self.acc._monitor = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def read_noise(path: str, threshold: float) -> tuple[dict, np.ndarray, np.ndarray, np.ndarray]:
+    """(report, tile_max, tile_above, map) of a monitor's side file, by the host-only rt_noise_blob_*
+    functions (no context, no GPU); the report also carries the header's fields, as Accumulator.info()."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    i = rt_accum_info()
+    rc = lib().rt_noise_blob_info(blob, len(blob), ctypes.byref(i))
+    if rc != 0:
+        raise RtError(f"rt_noise_blob_info({path!r}) failed ({rc})", rc)
+    d = i.as_dict()
+    rows, width = d["n_values"] // (3 * d["width"]), d["width"]
+    ty, tx = (rows + 15) // 16, (width + 15) // 16
+    tile_max, tile_above = np.zeros((ty, tx), np.float32), np.zeros((ty, tx), np.int32)
+    nmap = np.zeros((rows, width), np.float32)
+    rep = rt_noise_report()
+    rc = lib().rt_noise_blob_measure(blob, len(blob), threshold, ctypes.byref(rep), tile_max.ctypes.data,
+                                     tile_above.ctypes.data, nmap.ctypes.data)
+    if rc != 0:
+        raise RtError(f"rt_noise_blob_measure({path!r}) failed ({rc})", rc)
+    return {**d, **rep.as_dict()}, tile_max, tile_above, nmap
 
 
 def read_checkpoint(path: str) -> tuple[dict, np.ndarray]:
@@ -579,22 +721,44 @@ def read_checkpoint(path: str) -> tuple[dict, np.ndarray]:
 
 def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context | None = None, every: int = 1,
                      on_image=None, checkpoint: str | None = None, chunk_fbs: int | None = None,
-                     cam_mode: int = RT_CAM_REF_SLOT0, seed: int = 1984) -> tuple[np.ndarray, dict]:
+                     cam_mode: int = RT_CAM_REF_SLOT0, seed: int = 1984, until_noise: float | None = None,
+                     noisy_fraction: float = 0.01, min_fbs: int = 2, on_noise=None) -> tuple[np.ndarray, dict]:
     """draw() of render.h:118-174 in steps of `every` frame buffers: after each step
     on_image(image, fbs_done) gets the PNG-order image so far (the reference leaves tmp/<id>.ppm
     behind, render.h:152-162) and, with a checkpoint path, the state is saved there (temporary name,
     then rename).  An existing checkpoint of the same scene and settings is continued; one of another
     scene or other settings raises.  Returns (final image, counters of the frame buffers rendered by
     this call); the image is byte-identical to draw()'s.  chunk_fbs: frame buffers per render launch
-    (default: every)."""
+    (default: every).
+
+    until_noise=T attaches a noise monitor (NoiseMonitor; None changes nothing).  After each step
+    with done >= max(2, min_fbs) frame buffers it is measured with threshold T (8-bit output levels),
+    on_noise(report, done) is called, and the draw stops early once pixels_above <=
+    floor(noisy_fraction * pixels); settings.no_fb stays the upper limit.  The image returned after
+    `done` frame buffers is byte-identical to draw() with no_fb = done.  With a checkpoint the monitor
+    is saved to checkpoint + ".noise" before the checkpoint itself, and a resumed draw is measured
+    before it renders anything (a draw that had converged stays stopped).  Resuming needs that side
+    file: a missing one, or one whose header differs from the checkpoint's, raises RtError -- the
+    statistics are never silently restarted from a later frame buffer."""
     if settings.image_height <= 0:
         settings.aspect_ratio = curr_scene.aspect
         settings.calc_all()
     if every < 1:
         raise ValueError("every < 1")
+    if until_noise is not None and settings.no_fb > NOISE_MAX_FBS:
+        raise ValueError(f"a noise monitor accepts at most {NOISE_MAX_FBS} frame buffers")
     own = ctx is None
     ctx = ctx or Context(0)
-    acc = None
+    acc = mon = None
+
+    def converged() -> bool:
+        if mon is None or acc.done < max(2, min_fbs):
+            return False
+        report = mon.measure(until_noise)[0]
+        if on_noise is not None:
+            on_noise(report, acc.done)
+        return report["pixels_above"] <= math.floor(noisy_fraction * report["pixels"])
+
     try:
         ctx.upload(curr_scene)
         args = make_args(settings.image_width, settings.image_height, settings.samples_per_pixel_per_fb,
@@ -606,16 +770,28 @@ def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context 
             differ = [k for k in want if k not in ("fb_count", "n_values", "scene_fp") and got[k] != want[k]]
             if differ or got["fb_count"] > settings.no_fb:
                 raise RtError(f"checkpoint {checkpoint!r} is of another draw: {differ or 'more frame buffers'}")
+            if until_noise is not None:
+                side = checkpoint + ".noise"
+                if not os.path.exists(side):
+                    raise RtError(f"checkpoint {checkpoint!r} has no noise side file {side!r}: the draw cannot "
+                                  "continue with until_noise (the statistics must cover every frame buffer)")
+                mon = NoiseMonitor.load(acc, side)
         else:
             acc = ctx.accumulator(args, chunk)
+            if until_noise is not None:
+                mon = acc.noise_monitor()
         total = rt_counters().as_dict()
         img = acc.image(png_order=True) if acc.done else None
-        while acc.done < settings.no_fb:
+        stop = acc.done > 0 and converged()
+        while acc.done < settings.no_fb and not stop:
             cnt = acc.add(min(every, settings.no_fb - acc.done))
             total = {k: total[k] + cnt[k] for k in total}
             img = acc.image(png_order=True)
             if checkpoint:
+                if mon is not None:
+                    mon.save(checkpoint + ".noise")
                 acc.save(checkpoint)
+            stop = converged()
             if on_image is not None:
                 on_image(img, acc.done)
         return img, total

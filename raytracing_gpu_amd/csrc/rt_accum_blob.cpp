@@ -70,13 +70,7 @@ int64_t owned_row_count(const rt_render_args* a) {
   return owned * rows - (owns_last ? bands * rows - a->height : 0);
 }
 
-}  // namespace rtacc
-
 namespace {
-
-const char kMagic[8] = {'R', 'T', 'A', 'C', 'C', 'U', 'M', '1'};
-constexpr uint32_t kVersion = 1;
-
 void put32(unsigned char* p, uint32_t v) {
   for (int k = 0; k < 4; ++k) p[k] = (unsigned char)(v >> (8 * k));
 }
@@ -93,6 +87,7 @@ uint64_t get64(const unsigned char* p) {
   for (int k = 0; k < 8; ++k) v |= (uint64_t)p[k] << (8 * k);
   return v;
 }
+}  // namespace
 
 // What a header may hold: render arguments rt_render accepts (fb_count >= 0 here: the frame buffers
 // done) and the value count of their tiling.
@@ -100,10 +95,47 @@ bool info_ok(const rt_accum_info* i) {
   const rt_render_args& a = i->args;
   if (a.width <= 0 || a.height <= 0 || a.spp <= 0 || a.fb_first < 0 || a.fb_count < 0 || a.max_depth <= 0) return false;
   if (a.cam_mode != RT_CAM_REF_SLOT0 && a.cam_mode != RT_CAM_PER_PIXEL) return false;
-  const int64_t rows = rtacc::owned_row_count(&a);
+  const int64_t rows = owned_row_count(&a);
   // rows, width < 2^31: rows x width fits 64 bits, the factor 3 is checked by division
   return rows > 0 && i->n_values % 3 == 0 && i->n_values / 3 == rows * a.width;
 }
+
+void put_header(unsigned char* p, const char* magic, uint32_t version, const rt_accum_info* info, uint64_t payload_hash) {
+  memcpy(p, magic, 8);
+  put32(p + 8, version);
+  put32(p + 12, (uint32_t)kHeaderBytes);
+  const rt_render_args& a = info->args;
+  const int32_t f[12] = {a.width,    a.height,    a.spp,        a.fb_first,   a.fb_count, a.max_depth,
+                         a.cam_mode, a.band_rows, a.band_first, a.band_stride, a.stats,   a.flags};
+  for (int k = 0; k < 12; ++k) put32(p + 16 + 4 * k, (uint32_t)f[k]);
+  put64(p + 64, a.seed);
+  put64(p + 72, (uint64_t)info->n_values);
+  put64(p + 80, info->scene_fp);
+  put64(p + 88, payload_hash);
+}
+
+bool get_header(const unsigned char* p, const char* magic, uint32_t version, rt_accum_info* info, uint64_t* payload_hash) {
+  if (memcmp(p, magic, 8) != 0 || get32(p + 8) != version || get32(p + 12) != kHeaderBytes) return false;
+  rt_accum_info i = {};
+  int32_t f[12];
+  for (int k = 0; k < 12; ++k) f[k] = (int32_t)get32(p + 16 + 4 * k);
+  rt_render_args& a = i.args;
+  a.width = f[0], a.height = f[1], a.spp = f[2], a.fb_first = f[3], a.fb_count = f[4], a.max_depth = f[5];
+  a.cam_mode = f[6], a.band_rows = f[7], a.band_first = f[8], a.band_stride = f[9], a.stats = f[10], a.flags = f[11];
+  a.seed = get64(p + 64);
+  i.n_values = (int64_t)get64(p + 72);
+  i.scene_fp = get64(p + 80);
+  *payload_hash = get64(p + 88);
+  *info = i;
+  return true;
+}
+
+}  // namespace rtacc
+
+namespace {
+
+const char kMagic[8] = {'R', 'T', 'A', 'C', 'C', 'U', 'M', '1'};
+constexpr uint32_t kVersion = 1;
 
 // write_frame_buffer's quantisation (color.h:40-44) as the device code has it; NaN defined as 0.
 int quant(float x) {
@@ -118,44 +150,27 @@ int quant(float x) {
 extern "C" {
 
 int rt_accum_blob_pack(const rt_accum_info* info, const float* sums, void* blob, size_t cap, size_t* need) {
-  if (!info || !info_ok(info)) return RT_ERR_ARG;
+  if (!info || !rtacc::info_ok(info)) return RT_ERR_ARG;
   const size_t payload = (size_t)info->n_values * sizeof(float), total = rtacc::kHeaderBytes + payload;
   if (need) *need = total;
   if (!blob && cap == 0) return RT_OK;  // size query
   if (!blob || !sums || cap < total) return RT_ERR_ARG;
   unsigned char* p = static_cast<unsigned char*>(blob);
-  memcpy(p, kMagic, 8);
-  put32(p + 8, kVersion);
-  put32(p + 12, (uint32_t)rtacc::kHeaderBytes);
-  const rt_render_args& a = info->args;
-  const int32_t f[12] = {a.width,    a.height,    a.spp,        a.fb_first,   a.fb_count, a.max_depth,
-                         a.cam_mode, a.band_rows, a.band_first, a.band_stride, a.stats,   a.flags};
-  for (int k = 0; k < 12; ++k) put32(p + 16 + 4 * k, (uint32_t)f[k]);
-  put64(p + 64, a.seed);
-  put64(p + 72, (uint64_t)info->n_values);
-  put64(p + 80, info->scene_fp);
   memmove(p + rtacc::kHeaderBytes, sums, payload);
-  put64(p + 88, rtacc::fnv1a(p + rtacc::kHeaderBytes, payload));
+  rtacc::put_header(p, kMagic, kVersion, info, rtacc::fnv1a(p + rtacc::kHeaderBytes, payload));
   return RT_OK;
 }
 
 int rt_accum_blob_info(const void* blob, size_t n, rt_accum_info* info) {
   if (!blob || !info || n < rtacc::kHeaderBytes) return RT_ERR_ARG;
   const unsigned char* p = static_cast<const unsigned char*>(blob);
-  if (memcmp(p, kMagic, 8) != 0 || get32(p + 8) != kVersion || get32(p + 12) != rtacc::kHeaderBytes) return RT_ERR_ARG;
   rt_accum_info i = {};
-  int32_t f[12];
-  for (int k = 0; k < 12; ++k) f[k] = (int32_t)get32(p + 16 + 4 * k);
-  rt_render_args& a = i.args;
-  a.width = f[0], a.height = f[1], a.spp = f[2], a.fb_first = f[3], a.fb_count = f[4], a.max_depth = f[5];
-  a.cam_mode = f[6], a.band_rows = f[7], a.band_first = f[8], a.band_stride = f[9], a.stats = f[10], a.flags = f[11];
-  a.seed = get64(p + 64);
-  i.n_values = (int64_t)get64(p + 72);
-  i.scene_fp = get64(p + 80);
-  if (!info_ok(&i)) return RT_ERR_ARG;
+  uint64_t hash = 0;
+  if (!rtacc::get_header(p, kMagic, kVersion, &i, &hash)) return RT_ERR_ARG;
+  if (!rtacc::info_ok(&i)) return RT_ERR_ARG;
   const size_t payload = (size_t)i.n_values * sizeof(float);
   if (n - rtacc::kHeaderBytes != payload) return RT_ERR_ARG;
-  if (rtacc::fnv1a(p + rtacc::kHeaderBytes, payload) != get64(p + 88)) return RT_ERR_ARG;
+  if (rtacc::fnv1a(p + rtacc::kHeaderBytes, payload) != hash) return RT_ERR_ARG;
   *info = i;
   return RT_OK;
 }

@@ -2718,6 +2718,154 @@ __global__ __launch_bounds__(kBlock) void accum_add_kernel(const float* __restri
   }
 }
 
+// accum_add_kernel with a noise monitor attached (rt_noise, include/rt_hip.h): the same single pass
+// over the frame buffers, the float sums updated by the same float operations in the same order
+// (byte-identical sums), and per value the integer moments S1 += c^2 (u32), S2 += c^4 (u64).  A fold
+// is refused before launch when the monitor would pass 32768 frame buffers, so S1 <= 2^15 x 65025
+// < 2^31 and S2 <= 2^15 x 65025^2 < 2^47 never wrap.  Same layout: a lane owns 4 consecutive values;
+// VEC (per_fb % 4 == 0; fb, sums, s1, s2 16-byte aligned): one 16-byte load and store for the S1
+// quad, two 16-byte pairs for S2.  Traffic per value: 4 nfb bytes in, 8 + 8 + 16 bytes of state.
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void accum_add_stats_kernel(const float* __restrict__ fb, float* __restrict__ sums,
+                                                                uint32_t* __restrict__ s1, unsigned long long* __restrict__ s2,
+                                                                long long per_fb, int nfb) {
+  const long long k0 = 4 * ((long long)blockIdx.x * kBlock + threadIdx.x);
+  if (k0 >= per_fb) return;
+  if (VEC && k0 + 4 <= per_fb) {
+    float4 a = *reinterpret_cast<const float4*>(sums + k0);
+    uint4 m1 = *reinterpret_cast<const uint4*>(s1 + k0);
+    ulonglong2 m2a = *reinterpret_cast<const ulonglong2*>(s2 + k0);
+    ulonglong2 m2b = *reinterpret_cast<const ulonglong2*>(s2 + k0 + 2);
+#pragma unroll 4
+    for (int f = 0; f < nfb; ++f) {
+      const float4 v = *reinterpret_cast<const float4*>(fb + (long long)f * per_fb + k0);
+      const int cx = quant(v.x), cy = quant(v.y), cz = quant(v.z), cw = quant(v.w);
+      a.x += (float)(cx * cx) / (255.0f * 255.0f);
+      a.y += (float)(cy * cy) / (255.0f * 255.0f);
+      a.z += (float)(cz * cz) / (255.0f * 255.0f);
+      a.w += (float)(cw * cw) / (255.0f * 255.0f);
+      const uint32_t qx = (uint32_t)(cx * cx), qy = (uint32_t)(cy * cy), qz = (uint32_t)(cz * cz), qw = (uint32_t)(cw * cw);
+      m1.x += qx;
+      m1.y += qy;
+      m1.z += qz;
+      m1.w += qw;
+      m2a.x += (unsigned long long)qx * qx;
+      m2a.y += (unsigned long long)qy * qy;
+      m2b.x += (unsigned long long)qz * qz;
+      m2b.y += (unsigned long long)qw * qw;
+    }
+    *reinterpret_cast<float4*>(sums + k0) = a;
+    *reinterpret_cast<uint4*>(s1 + k0) = m1;
+    *reinterpret_cast<ulonglong2*>(s2 + k0) = m2a;
+    *reinterpret_cast<ulonglong2*>(s2 + k0 + 2) = m2b;
+    return;
+  }
+  const long long k1 = k0 + 4 < per_fb ? k0 + 4 : per_fb;
+  for (long long k = k0; k < k1; ++k) {
+    float a = sums[k];
+    uint32_t m1 = s1[k];
+    unsigned long long m2 = s2[k];
+    for (int f = 0; f < nfb; ++f) {
+      const int c = quant(fb[(long long)f * per_fb + k]);
+      a += (float)(c * c) / (255.0f * 255.0f);
+      const uint32_t q = (uint32_t)(c * c);
+      m1 += q;
+      m2 += (unsigned long long)q * q;
+    }
+    sums[k] = a;
+    s1[k] = m1;
+    s2[k] = m2;
+  }
+}
+
+// The noise of the n frame buffers a monitor has seen (definitions in include/rt_hip.h).  One
+// 256-lane workgroup per tile of 16 x 16 pixels over (owned-row index, column), one lane per pixel;
+// a wave holds 4 tile rows of 16 pixels.  Per pixel, over its channels j, in unsigned 64-bit
+// integers (n <= 32768: n S2 and S1^2 <= 4.6e18 each, the three-channel sum <= 1.4e19 < 2^64; every
+// term n S2 - S1^2 >= 0 by Cauchy-Schwarz):  D = sum_j (n S2_j - S1_j^2),  S = sum_j S1_j;  then in
+// double, in this order:  a = D / (3.0 n n (n - 1) 4228250625.0),  m = max(S / (3.0 n 65025.0), 2^-16),
+// noise = float(128.0 sqrt(a / m)) >= 0.  Lanes outside a partial tile hold noise 0 and are not
+// counted.  Outputs: map[row][col] (may be null); per tile the maximum (shuffles within the wave, LDS
+// across the four) and the count of pixels with noise > threshold (ballot + popcount).  The image-wide
+// maximum and count come from the tile arrays in noise_reduce_kernel (one atomic per tile on one
+// address serialises: 32 400 tiles at 3840 x 2159 took longer than reading the moments).  No float is
+// summed anywhere: every output is independent of the order of reduction.
+__global__ __launch_bounds__(256) void noise_measure_kernel(const uint32_t* __restrict__ s1,
+                                                            const unsigned long long* __restrict__ s2, int n, int rows,
+                                                            int width, float threshold, float* __restrict__ map,
+                                                            float* __restrict__ tile_max, int32_t* __restrict__ tile_above) {
+  __shared__ float wave_max[4];
+  __shared__ int wave_above[4];
+  const int lane = threadIdx.x;
+  const int col = blockIdx.x * 16 + (lane & 15), row = blockIdx.y * 16 + (lane >> 4);
+  const bool valid = col < width && row < rows;
+  float noise = 0.0f;
+  if (valid) {
+    const long long px = (long long)row * width + col;
+    unsigned long long D = 0, S = 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const unsigned long long m1 = s1[3 * px + j], m2 = s2[3 * px + j];
+      D += (unsigned long long)n * m2 - m1 * m1;
+      S += m1;
+    }
+    const double dn = (double)n, dn1 = (double)(n - 1);
+    const double a = (double)D / (3.0 * dn * dn * dn1 * 4228250625.0);
+    double m = (double)S / (3.0 * dn * 65025.0);
+    if (m < 0x1p-16) m = 0x1p-16;
+    noise = (float)(128.0 * __builtin_sqrt(a / m));
+    if (map) map[px] = noise;
+  }
+  const unsigned long long hot = __ballot(valid && noise > threshold);
+  float mx = noise;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
+  const int wave = lane >> 6;
+  if ((lane & 63) == 0) {
+    wave_max[wave] = mx;
+    wave_above[wave] = __popcll(hot);
+  }
+  __syncthreads();
+  if (lane == 0) {
+    const float t = fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]));
+    const int cnt = wave_above[0] + wave_above[1] + wave_above[2] + wave_above[3];
+    const int tile = blockIdx.y * gridDim.x + blockIdx.x;
+    tile_max[tile] = t;
+    tile_above[tile] = cnt;
+  }
+}
+
+// Image-wide maximum (as the bit pattern of the non-negative float, in the low word of totals[1]) and
+// count (totals[0]) from noise_measure_kernel's tile arrays: one 256-lane workgroup strides over the
+// tiles; a maximum and an integer sum, so the order does not matter.
+__global__ __launch_bounds__(256) void noise_reduce_kernel(const float* __restrict__ tile_max,
+                                                           const int32_t* __restrict__ tile_above, int tiles,
+                                                           unsigned long long* __restrict__ totals) {
+  __shared__ float wave_max[4];
+  __shared__ unsigned long long wave_above[4];
+  const int lane = threadIdx.x;
+  float mx = 0.0f;
+  unsigned long long cnt = 0;
+  for (int t = lane; t < tiles; t += 256) {
+    mx = fmaxf(mx, tile_max[t]);
+    cnt += (unsigned long long)tile_above[t];
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    mx = fmaxf(mx, __shfl_xor(mx, d));
+    cnt += __shfl_xor(cnt, d);
+  }
+  if ((lane & 63) == 0) {
+    wave_max[lane >> 6] = mx;
+    wave_above[lane >> 6] = cnt;
+  }
+  __syncthreads();
+  if (lane == 0) {
+    totals[0] = wave_above[0] + wave_above[1] + wave_above[2] + wave_above[3];
+    totals[1] = __float_as_uint(fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3])));
+  }
+}
+
 // The image of the nfb frame buffers folded into sums: resolve_kernel's last line.  VEC (sums 16-byte,
 // out 4-byte aligned): 4 sums in, 4 bytes out per lane.
 template <bool VEC>
@@ -5055,9 +5203,28 @@ struct rt_accum {
   // around the last accumulate launch (ev[0], ev[1]) and the last image launch (ev[2], ev[3])
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool add_timed = false, image_timed = false;
+  rt_noise* noise = nullptr;  // the attached monitor (not owned: rt_noise_destroy frees it)
+};
+
+// Noise monitor of an accumulator (include/rt_hip.h): the integer moments of c^2 per accumulator value.
+struct rt_noise {
+  rt_accum* acc = nullptr;  // null once the accumulator is destroyed (detached: calls are RT_ERR_STATE)
+  int device = 0;
+  long long per_fb = 0;     // the accumulator's
+  int rows = 0, width = 0, tiles_x = 0, tiles_y = 0;
+  int32_t fbs = 0;          // frame buffers folded in, at most rtacc::kNoiseMaxFbs
+  uint32_t* s1 = nullptr;            // [per_fb] sum of c^2
+  unsigned long long* s2 = nullptr;  // [per_fb] sum of c^4
+  // measure outputs: [tiles] maxima, [tiles] counts, then the image-wide count (u64) and maximum (u32 bits)
+  float* tile_max = nullptr;
+  int32_t* tile_above = nullptr;
+  unsigned long long* totals = nullptr;  // totals[0] = pixels above, low word of totals[1] = max bits
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool timed = false;
 };
 
 extern "C" int rt_accum_destroy(rt_accum* acc);
+extern "C" int rt_noise_destroy(rt_noise* nm);
 
 namespace {
 
@@ -5068,8 +5235,17 @@ int accum_fold(rt_accum* acc, const float* fb_dev, int count) {
   rt_ctx* c = acc->ctx;
   const long long per_fb = acc->per_fb;
   const unsigned blocks = (unsigned)(((per_fb + 3) / 4 + kBlock - 1) / kBlock);
+  rt_noise* nm = acc->noise;
+  if (nm && count > rtacc::kNoiseMaxFbs - nm->fbs) return fail(c, RT_ERR_ARG, "noise monitor: more than 32768 frame buffers");
   HIPCHK(c, hipEventRecord(acc->ev[0], c->stream));
-  if (per_fb % 4 == 0 && aligned_to(fb_dev, 16) && aligned_to(acc->sums, 16))
+  const bool vec = per_fb % 4 == 0 && aligned_to(fb_dev, 16) && aligned_to(acc->sums, 16);
+  if (nm && vec && aligned_to(nm->s1, 16) && aligned_to(nm->s2, 16))
+    hipLaunchKernelGGL(accum_add_stats_kernel<true>, dim3(blocks), dim3(kBlock), 0, c->stream, fb_dev, acc->sums, nm->s1,
+                       nm->s2, per_fb, count);
+  else if (nm)
+    hipLaunchKernelGGL(accum_add_stats_kernel<false>, dim3(blocks), dim3(kBlock), 0, c->stream, fb_dev, acc->sums, nm->s1,
+                       nm->s2, per_fb, count);
+  else if (vec)
     hipLaunchKernelGGL(accum_add_kernel<true>, dim3(blocks), dim3(kBlock), 0, c->stream, fb_dev, acc->sums, per_fb, count);
   else
     hipLaunchKernelGGL(accum_add_kernel<false>, dim3(blocks), dim3(kBlock), 0, c->stream, fb_dev, acc->sums, per_fb, count);
@@ -5077,7 +5253,14 @@ int accum_fold(rt_accum* acc, const float* fb_dev, int count) {
   HIPCHK(c, hipEventRecord(acc->ev[1], c->stream));
   acc->add_timed = true;
   acc->args.fb_count += count;
+  if (nm) nm->fbs += count;
   return RT_OK;
+}
+
+// A fold of count frame buffers that the attached monitor would refuse (checked before anything is
+// rendered or written).
+bool noise_full(const rt_accum* acc, int32_t count) {
+  return acc->noise && count > rtacc::kNoiseMaxFbs - acc->noise->fbs;
 }
 
 int accum_new(rt_ctx* c, const rt_render_args* a, int32_t chunk_fbs, rt_accum** out) {
@@ -5134,6 +5317,7 @@ int rt_accum_destroy(rt_accum* acc) {
   if (!acc) return RT_ERR_ARG;
   (void)hipSetDevice(acc->ctx->device);
   (void)hipStreamSynchronize(acc->ctx->stream);
+  if (acc->noise) acc->noise->acc = nullptr;  // detached: the monitor's calls fail from here on
   if (acc->sums) (void)hipFree(acc->sums);
   if (acc->scratch) (void)hipFree(acc->scratch);
   if (acc->img) (void)hipFree(acc->img);
@@ -5148,6 +5332,7 @@ int rt_accum_add(rt_accum* acc, int32_t count, rt_counters* counters) {
   rt_ctx* c = acc->ctx;
   if (count < 1) return fail(c, RT_ERR_ARG, "count < 1");
   if (count > INT32_MAX - acc->args.fb_first - acc->args.fb_count) return fail(c, RT_ERR_ARG, "fb range overflows");
+  if (noise_full(acc, count)) return fail(c, RT_ERR_ARG, "noise monitor: more than 32768 frame buffers");
   if (acc->scene_gen != c->scene_gen) return fail(c, RT_ERR_STATE, "scene uploaded again since the accumulator was created");
   HIPCHK(c, hipSetDevice(c->device));
   const rt_render_args& a = acc->args;
@@ -5188,6 +5373,7 @@ int rt_accum_add_fbs(rt_accum* acc, const float* fb, int32_t count) {
   if (!fb) return fail(c, RT_ERR_ARG, "null fb");
   if (count < 1) return fail(c, RT_ERR_ARG, "count < 1");
   if (count > INT32_MAX - acc->args.fb_first - acc->args.fb_count) return fail(c, RT_ERR_ARG, "fb range overflows");
+  if (noise_full(acc, count)) return fail(c, RT_ERR_ARG, "noise monitor: more than 32768 frame buffers");
   HIPCHK(c, hipSetDevice(c->device));
   int rc = RT_OK;
   float* tmp = nullptr;  // a host frame buffer is staged through device memory, as rt_resolve does
@@ -5306,6 +5492,206 @@ int rt_accum_load(rt_ctx* c, const void* blob, size_t n, int32_t chunk_fbs, rt_a
   }
   acc->args.fb_count = info.args.fb_count;
   *out = acc;
+  return RT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------- noise monitor
+namespace {
+
+// A monitor attached to acc with every moment 0 (queued on the context's stream).
+int noise_new(rt_accum* acc, rt_noise** out) {
+  rt_ctx* c = acc->ctx;
+  const long long rows = acc->per_fb / (3LL * acc->args.width);
+  const long long tiles_x = (acc->args.width + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
+  const long long tiles_y = (rows + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
+  if (tiles_y > 65535 || tiles_x * tiles_y > INT32_MAX) return fail(c, RT_ERR_ARG, "noise monitor: too many tiles");
+  HIPCHK(c, hipSetDevice(c->device));
+  rt_noise* nm = new rt_noise;
+  nm->device = c->device;
+  nm->per_fb = acc->per_fb;
+  nm->rows = (int)rows;
+  nm->width = acc->args.width;
+  nm->tiles_x = (int)tiles_x;
+  nm->tiles_y = (int)tiles_y;
+  const size_t nv = (size_t)acc->per_fb, tiles = (size_t)(tiles_x * tiles_y);
+  bool ok = hipMalloc((void**)&nm->s1, nv * sizeof(uint32_t)) == hipSuccess;
+  ok = ok && hipMalloc((void**)&nm->s2, nv * sizeof(unsigned long long)) == hipSuccess;
+  ok = ok && hipMalloc((void**)&nm->tile_max, tiles * sizeof(float)) == hipSuccess;
+  ok = ok && hipMalloc((void**)&nm->tile_above, tiles * sizeof(int32_t)) == hipSuccess;
+  ok = ok && hipMalloc((void**)&nm->totals, 2 * sizeof(unsigned long long)) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    rt_noise_destroy(nm);
+    return fail(c, RT_ERR_NOMEM, "hipMalloc noise monitor");
+  }
+  ok = hipEventCreate(&nm->ev[0]) == hipSuccess && hipEventCreate(&nm->ev[1]) == hipSuccess;
+  ok = ok && hipMemsetAsync(nm->s1, 0, nv * sizeof(uint32_t), c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(nm->s2, 0, nv * sizeof(unsigned long long), c->stream) == hipSuccess;
+  if (!ok) {
+    rt_noise_destroy(nm);
+    return fail(c, RT_ERR_HIP, "set up noise monitor");
+  }
+  nm->acc = acc;
+  acc->noise = nm;
+  *out = nm;
+  return RT_OK;
+}
+
+// noise_measure_kernel over the whole monitor, then the reduction of its tile arrays, queued on the
+// context's stream; map_dev may be null.
+int noise_run(rt_noise* nm, float threshold, float* map_dev) {
+  rt_ctx* c = nm->acc->ctx;
+  HIPCHK(c, hipEventRecord(nm->ev[0], c->stream));
+  hipLaunchKernelGGL(noise_measure_kernel, dim3(nm->tiles_x, nm->tiles_y), dim3(256), 0, c->stream, nm->s1, nm->s2, nm->fbs,
+                     nm->rows, nm->width, threshold, map_dev, nm->tile_max, nm->tile_above);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(noise_reduce_kernel, dim3(1), dim3(256), 0, c->stream, nm->tile_max, nm->tile_above,
+                     nm->tiles_x * nm->tiles_y, nm->totals);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(nm->ev[1], c->stream));
+  nm->timed = true;
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_noise_create(rt_accum* acc, rt_noise** out) {
+  if (!acc) return RT_ERR_ARG;
+  rt_ctx* c = acc->ctx;
+  if (!out) return fail(c, RT_ERR_ARG, "null monitor pointer");
+  *out = nullptr;
+  if (acc->noise) return fail(c, RT_ERR_STATE, "the accumulator has a noise monitor already");
+  if (acc->args.fb_count != 0) return fail(c, RT_ERR_STATE, "a noise monitor sees every frame buffer or none: the accumulator is not empty");
+  return noise_new(acc, out);
+}
+
+int rt_noise_destroy(rt_noise* nm) {
+  if (!nm) return RT_ERR_ARG;
+  (void)hipSetDevice(nm->device);
+  if (nm->acc) {
+    (void)hipStreamSynchronize(nm->acc->ctx->stream);
+    nm->acc->noise = nullptr;  // the accumulator goes on with accum_add_kernel
+  }
+  if (nm->s1) (void)hipFree(nm->s1);
+  if (nm->s2) (void)hipFree(nm->s2);
+  if (nm->tile_max) (void)hipFree(nm->tile_max);
+  if (nm->tile_above) (void)hipFree(nm->tile_above);
+  if (nm->totals) (void)hipFree(nm->totals);
+  for (hipEvent_t e : nm->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete nm;
+  return RT_OK;
+}
+
+int rt_noise_measure(rt_noise* nm, float threshold, rt_noise_report* rep, float* tile_max, int32_t* tile_above) {
+  if (!nm) return RT_ERR_ARG;
+  if (!nm->acc) return RT_ERR_STATE;  // detached
+  rt_ctx* c = nm->acc->ctx;
+  if (nm->fbs < 2) return fail(c, RT_ERR_STATE, "noise needs at least 2 frame buffers");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = noise_run(nm, threshold, nullptr);
+  if (rc) return rc;
+  const size_t tiles = (size_t)nm->tiles_x * nm->tiles_y;
+  unsigned long long totals[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(totals, nm->totals, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
+  if (tile_max) HIPCHK(c, hipMemcpyAsync(tile_max, nm->tile_max, tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (tile_above) HIPCHK(c, hipMemcpyAsync(tile_above, nm->tile_above, tiles * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (rep) {
+    rep->fbs = nm->fbs;
+    rep->tiles_x = nm->tiles_x;
+    rep->tiles_y = nm->tiles_y;
+    rep->pad = 0;
+    rep->pixels = (int64_t)nm->rows * nm->width;
+    rep->pixels_above = (int64_t)totals[0];
+    rep->threshold = threshold;
+    const uint32_t bits = (uint32_t)totals[1];
+    memcpy(&rep->max_noise, &bits, sizeof(bits));
+  }
+  return RT_OK;
+}
+
+int rt_noise_map(rt_noise* nm, float* out) {
+  if (!nm) return RT_ERR_ARG;
+  if (!nm->acc) return RT_ERR_STATE;  // detached
+  rt_ctx* c = nm->acc->ctx;
+  if (!out) return fail(c, RT_ERR_ARG, "null map");
+  if (nm->fbs < 2) return fail(c, RT_ERR_STATE, "noise needs at least 2 frame buffers");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)nm->rows * nm->width * sizeof(float);
+  float* tmp = nullptr;  // a host map is staged through device memory
+  if (!device_ptr(out) && hipMalloc((void**)&tmp, bytes) != hipSuccess) return fail(c, RT_ERR_NOMEM, "hipMalloc noise map");
+  int rc = noise_run(nm, 0.0f, tmp ? tmp : out);
+  if (!rc && tmp && hipMemcpyAsync(out, tmp, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+    rc = fail(c, RT_ERR_HIP, "copy noise map");
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(c, RT_ERR_HIP, "noise measure kernel");
+  if (tmp) (void)hipFree(tmp);
+  return rc;
+}
+
+float rt_noise_last_measure_ms(const rt_noise* nm) {
+  float ms = 0.0f;
+  if (!nm || !nm->timed || hipEventElapsedTime(&ms, nm->ev[0], nm->ev[1]) != hipSuccess) return 0.0f;
+  return ms;
+}
+
+int rt_noise_save(rt_noise* nm, void* blob, size_t cap, size_t* need) {
+  if (!nm) return RT_ERR_ARG;
+  if (!nm->acc) return RT_ERR_STATE;  // detached
+  rt_ctx* c = nm->acc->ctx;
+  const size_t nv = (size_t)nm->per_fb;
+  const size_t total = rtacc::kHeaderBytes + nv * (sizeof(unsigned long long) + sizeof(uint32_t));
+  if (need) *need = total;
+  if (!blob && cap == 0) return RT_OK;  // size query
+  if (!blob || cap < total) return fail(c, RT_ERR_ARG, "noise blob buffer too small");
+  HIPCHK(c, hipSetDevice(c->device));
+  // the moments land in the blob's payload, then the header is packed around them
+  unsigned char* p2 = static_cast<unsigned char*>(blob) + rtacc::kHeaderBytes;
+  unsigned char* p1 = p2 + nv * sizeof(unsigned long long);
+  HIPCHK(c, hipMemcpyAsync(p2, nm->s2, nv * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(p1, nm->s1, nv * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  rt_accum_info info;
+  rt_accum_get_info(nm->acc, &info);
+  info.args.fb_count = nm->fbs;
+  if (rt_noise_blob_pack(&info, reinterpret_cast<const uint32_t*>(p1), reinterpret_cast<const uint64_t*>(p2), blob, cap, nullptr))
+    return fail(c, RT_ERR_ARG, "pack noise blob");
+  return RT_OK;
+}
+
+int rt_noise_load(rt_accum* acc, const void* blob, size_t n, rt_noise** out) {
+  if (!acc) return RT_ERR_ARG;
+  rt_ctx* c = acc->ctx;
+  if (!out) return fail(c, RT_ERR_ARG, "null monitor pointer");
+  *out = nullptr;
+  rt_accum_info info, have;
+  if (rt_noise_blob_info(blob, n, &info)) return fail(c, RT_ERR_ARG, "malformed noise blob");
+  if (acc->noise) return fail(c, RT_ERR_STATE, "the accumulator has a noise monitor already");
+  rt_accum_get_info(acc, &have);
+  const rt_render_args &a = info.args, &b = have.args;
+  if (a.width != b.width || a.height != b.height || a.spp != b.spp || a.fb_first != b.fb_first || a.fb_count != b.fb_count ||
+      a.max_depth != b.max_depth || a.cam_mode != b.cam_mode || a.band_rows != b.band_rows || a.band_first != b.band_first ||
+      a.band_stride != b.band_stride || a.stats != b.stats || a.flags != b.flags || a.seed != b.seed ||
+      info.n_values != have.n_values || info.scene_fp != have.scene_fp)
+    return fail(c, RT_ERR_STATE, "noise blob belongs to another accumulator state");
+  rt_noise* nm = nullptr;
+  int rc = noise_new(acc, &nm);
+  if (rc) return rc;
+  const size_t nv = (size_t)acc->per_fb;
+  const unsigned char* p2 = static_cast<const unsigned char*>(blob) + rtacc::kHeaderBytes;
+  const unsigned char* p1 = p2 + nv * sizeof(unsigned long long);
+  if (hipMemcpyAsync(nm->s2, p2, nv * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(nm->s1, p1, nv * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) {
+    rt_noise_destroy(nm);
+    return fail(c, RT_ERR_HIP, "copy noise moments to device");
+  }
+  nm->fbs = info.args.fb_count;
+  *out = nm;
   return RT_OK;
 }
 
