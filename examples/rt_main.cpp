@@ -8,6 +8,7 @@
 //     --band-rows B         rows per band for rt_multi (default 4)
 //     --repeat K            draw K times (the first draw is cold, later ones reuse the schedule)
 //     --depth D             max_depth (default 50)
+//     --height H            image height (default: WIDTH / the scene's aspect ratio, render.h:30)
 //     --obj PATH            mesh scenes: rt_obj_load (assimp's OBJ import, reference indexing)
 //     --tex PATH            texture for the mesh / earth scenes: rt_image_load (stb_image bytes)
 //     --progressive K       one GPU: draw through an rt_accum, K frame buffers per step; OUT.ppm is
@@ -22,6 +23,12 @@
 //                           the upper limit.  Each step's JSON line gains "noise_max" and "pixels_above",
 //                           a last line carries "stopped_at".  With --checkpoint FILE the monitor is
 //                           saved to FILE.noise before FILE, and resuming needs it
+//     --adaptive K          one GPU: draw through an rt_adapt, K frame buffers per step, rendering only the
+//     --until-noise T       16 x 16 tiles still active; from max(2, F) frame buffers on (--min-fbs F,
+//     --max-above M         default 4) every step retires the tiles with at most M (default 0) pixels of
+//     --min-fbs F           noise above T.  Each step prints one JSON line with "fbs", "tiles_active",
+//                           "pixel_fbs" and "noise_max"; a last line carries "stopped_at" and "pixel_fbs".
+//                           Ends when no tile is active or at NO_FB.  Not with --progressive / --checkpoint
 //
 // Writes OUT.ppm (binary P6, top row first) and one JSON line per draw on stdout.  Files written
 // more than once go to a temporary name first and are renamed into place.
@@ -177,13 +184,51 @@ int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int
   return 0;
 }
 
+// draw() through an adaptive accumulator: `step` frame buffers at a time for the tiles still active.
+int draw_adaptive(rt_ctx* ctx, const char* name, const rt_render_args& a, int step, const char* out,
+                  std::vector<uint8_t>& png, float noise_t, int max_above, int min_fbs) {
+  rt_adapt* ad = nullptr;
+  if (rt_adapt_create(ctx, &a, step, &ad)) return die("rt_adapt_create", rt_last_error(ctx));
+  char head[64];
+  snprintf(head, sizeof(head), "P6\n%d %d\n255\n", a.width, a.height);
+  rt_adapt_report rep = {};
+  rep.tiles_active = 1;
+  int done = 0;
+  while (done < a.fb_count && rep.tiles_active > 0) {
+    const auto t0 = std::chrono::steady_clock::now();
+    rt_counters c = {};
+    const int n = std::min(step, a.fb_count - done);
+    if (rt_adapt_add(ad, n, &c)) return die("rt_adapt_add", rt_last_error(ctx));
+    done += n;
+    const bool retire = done >= std::max(2, min_fbs);
+    if (retire && rt_adapt_retire(ad, noise_t, max_above, &rep)) return die("rt_adapt_retire", rt_last_error(ctx));
+    if (rt_adapt_image(ad, png.data(), 1)) return die("rt_adapt_image", rt_last_error(ctx));
+    if (!write_file(out, head, png.data(), png.size())) return die("write", out);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    printf("{\"fbs\": %d, \"scene\": \"%s\", \"width\": %d, \"height\": %d, \"wall_ms\": %.3f, \"segments\": %llu, "
+           "\"samples\": %llu",
+           done, name, a.width, a.height, ms, (unsigned long long)c.segments, (unsigned long long)c.samples);
+    if (retire)
+      printf(", \"tiles_active\": %d, \"pixel_fbs\": %lld, \"noise_max\": %.9g, \"pixels_above\": %lld", rep.tiles_active,
+             (long long)rep.pixel_fbs, rep.max_noise, (long long)rep.pixels_above);
+    printf("}\n");
+    fflush(stdout);
+  }
+  const long long pixel_fbs = done >= std::max(2, min_fbs) ? (long long)rep.pixel_fbs : (long long)a.width * a.height * done;
+  printf("{\"stopped_at\": %d, \"pixel_fbs\": %lld, \"tiles_active\": %d, \"until_noise\": %.9g, \"max_above\": %d}\n", done,
+         pixel_fbs, done >= std::max(2, min_fbs) ? rep.tiles_active : -1, noise_t, max_above);
+  fflush(stdout);
+  rt_adapt_destroy(ad);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc < 6) {
     fprintf(stderr, "usage: rt_main SCENE WIDTH SPP_PER_FB NO_FB OUT.ppm [--devices 0,1] [--gather rccl|host] "
-                    "[--band-rows B] [--repeat K] [--depth D] [--obj PATH] [--tex PATH] [--progressive K] [--checkpoint FILE] "
-                    "[--until-noise T [--noisy-fraction F]]\n");
+                    "[--band-rows B] [--repeat K] [--depth D] [--height H] [--obj PATH] [--tex PATH] [--progressive K] [--checkpoint FILE] "
+                    "[--until-noise T [--noisy-fraction F]] [--adaptive K --until-noise T [--max-above M] [--min-fbs F]]\n");
     return 2;
   }
   const char* name = argv[1];
@@ -195,7 +240,9 @@ int main(int argc, char** argv) {
   std::vector<int> devices;
   int gather = RT_GATHER_RCCL, band_rows = 4, repeat = 1;
   const char *obj_path = nullptr, *tex_path = nullptr, *ckpt_path = nullptr;
-  int progressive = 0;
+  int height = 0;
+  int progressive = 0, adaptive = 0, max_above = 0, min_fbs = 4;
+  bool have_adaptive = false, have_adaptive_opts = false;
   bool until_noise = false, have_fraction = false;
   float noise_t = 0.0f;
   double noisy_fraction = 0.01;
@@ -207,16 +254,29 @@ int main(int argc, char** argv) {
     else if (a == "--band-rows") band_rows = atoi(v), ++k;
     else if (a == "--repeat") repeat = atoi(v), ++k;
     else if (a == "--depth") s.max_depth = atoi(v), ++k;
+    else if (a == "--height") height = atoi(v), ++k;
     else if (a == "--obj") obj_path = v, ++k;
     else if (a == "--tex") tex_path = v, ++k;
     else if (a == "--progressive") progressive = atoi(v), ++k;
     else if (a == "--checkpoint") ckpt_path = v, ++k;
+    else if (a == "--adaptive") have_adaptive = true, adaptive = atoi(v), ++k;
+    else if (a == "--max-above") have_adaptive_opts = true, max_above = atoi(v), ++k;
+    else if (a == "--min-fbs") have_adaptive_opts = true, min_fbs = atoi(v), ++k;
     else if (a == "--until-noise") until_noise = true, noise_t = (float)atof(v), ++k;
     else if (a == "--noisy-fraction") have_fraction = true, noisy_fraction = atof(v), ++k;
     else return die("unknown option", argv[k]);
   }
 
-  if ((until_noise || have_fraction) && progressive <= 0) return die("--until-noise / --noisy-fraction", "need --progressive K");
+  if (have_adaptive) {
+    if (progressive != 0 || ckpt_path) return die("--adaptive", "cannot be combined with --progressive or --checkpoint");
+    if (have_fraction) return die("--adaptive", "retires tiles by --max-above, not --noisy-fraction");
+    if (!until_noise) return die("--adaptive", "needs --until-noise T");
+    if (adaptive < 1 || s.no_fb < 1) return die("--adaptive", "K and NO_FB must be at least 1");
+    if (max_above < 0) return die("--max-above", "must be at least 0");
+  } else if (have_adaptive_opts) {
+    return die("--max-above / --min-fbs", "need --adaptive K");
+  }
+  if (!have_adaptive && (until_noise || have_fraction) && progressive <= 0) return die("--until-noise / --noisy-fraction", "need --progressive K");
   if (have_fraction && !until_noise) return die("--noisy-fraction", "needs --until-noise T");
   if (until_noise && s.no_fb > 32768) return die("--until-noise", "a noise monitor accepts at most 32768 frame buffers");
 
@@ -250,6 +310,7 @@ int main(int argc, char** argv) {
   const rt_scene_soa* soa = rt_scene_view(scene);
   s.aspect_ratio = soa->aspect;  // main.cu:27
   s.calc_all();
+  if (height > 0) s.image_height = height;
 
   rt_render_args a = {};
   a.width = s.image_width;
@@ -275,6 +336,13 @@ int main(int argc, char** argv) {
     int rc = rt_multi_create((int)devices.size(), devices.data(), gather, &multi);
     if (rc) return die("rt_multi_create", gather == RT_GATHER_RCCL ? "RCCL communicator (distinct devices?)" : "");
     if (rt_multi_upload(multi, soa)) return die("rt_multi_upload", rt_multi_last_error(multi));
+  }
+  if (have_adaptive) {
+    if (!ctx) return die("--adaptive", "one GPU only (no --devices)");
+    const int rc = draw_adaptive(ctx, name, a, adaptive, out, png, noise_t, max_above, min_fbs);
+    rt_ctx_destroy(ctx);
+    rt_scene_free(scene);
+    return rc;
   }
   if (progressive != 0 || ckpt_path) {
     if (!ctx) return die("--progressive / --checkpoint", "one GPU only (no --devices)");

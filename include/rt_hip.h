@@ -473,6 +473,87 @@ int rt_noise_blob_pack(const rt_accum_info* info, const uint32_t* s1, const uint
 int rt_noise_blob_measure(const void* blob, size_t n, float threshold, rt_noise_report* rep,
                           float* tile_max, int32_t* tile_above, float* map);
 
+/* ------------------------------------------------------------------ launches over a set of tiles */
+/* rt_render for the pixels of the listed tiles only.  Tiles are the noise monitor's: 16 x 16 pixels over
+ * (owned-row index, column), row-major, id = ty * tiles_x + tx with tiles_x = ceil(width / 16) and
+ * tiles_y = ceil(owned_rows / 16); edge tiles are partial; for a band tiling the row index is the
+ * position in rt_owned_rows' list.  (They are not the 8 x 8 camera-ray tiles the kernels use inside.)
+ *
+ * fb has rt_render's layout for args, [fb_count][owned_rows][width][3], device or host pointer.  Every
+ * pixel of a listed tile receives, for every fb id of the call, exactly the floats rt_render writes there
+ * (a pixel's value depends on (fb id, pixel) alone); every other float of fb is left as it was (a host fb
+ * is copied to the device and back whole).  counters (may be NULL) receives the totals of the rendered
+ * items only.  tiles is a host array of n_tiles distinct ids.  RT_ERR_ARG, with fb untouched, for
+ * n_tiles <= 0, an id out of range, a repeated id, or fb_count x owned_rows x width > 2^31.
+ *
+ * The launch runs the kernel variant rt_render would pick for the scene and flags, over an item list
+ * built on the device.  It is isolated from the context's item schedule: no probe launch, no split
+ * samples, natural row order, nothing read from or recorded into the schedule of any configuration, so
+ * the rt_render launches around it run exactly as they would without it.  RT_FLAG_NO_SCHEDULE,
+ * RT_FLAG_NO_SPLIT and RT_FLAG_FRESH are accepted and have no effect; the other flags, stats, both
+ * camera modes and rt_ctx_options behave as in rt_render.  Afterwards rt_last_render_schedule is 0, and
+ * rt_last_render_kernel, rt_last_render_ms and rt_last_kernel_ms describe the tile launch. */
+int rt_render_tiles(rt_ctx* ctx, const rt_render_args* args, const int32_t* tiles, int32_t n_tiles, float* fb,
+                    rt_counters* counters);
+
+/* ------------------------------------------------------------------ adaptive accumulator */
+/* A progressive draw that stops rendering a tile (as above) once the tile's own noise estimate is low
+ * enough, and goes on with the others.  An object of its own beside rt_accum (no checkpoint format, no
+ * rt_multi support).  Per accumulator value it keeps the float sum of rt_accum (the same operations in
+ * the same order) and the integer moments S1, S2 of rt_noise: 16 bytes per value; per tile n_t, the
+ * number of frame buffers folded into it; and, from the first add, a scratch of chunk_fbs frame buffers
+ * with the item list of its launches.
+ *
+ * The guarantee: every pixel of tile t of the image is byte-identical to rt_draw with no_fb = n_t and
+ * the same fb_first (a pixel of frame buffer id depends on (id, pixel) alone, and the image after k frame
+ * buffers is quant(sum / k) with the sum taken in fb order).  The n_t are an output (rt_adapt_counts).
+ * They are determined by the sequence of add and retire calls alone -- retire decides on integer
+ * moments -- and depend neither on chunk_fbs nor on how the adds between two retires were split.
+ *
+ * What it does not give: stopping a tile on the spread of its own samples biases it slightly, towards
+ * stopping while it happens to look smooth (a rare bright path that has not occurred yet cannot show in
+ * the spread).  The only guard is the caller's: do not retire before enough frame buffers (min_fbs of
+ * the Python driver).  The reference has no adaptive mode to compare with. */
+typedef struct rt_adapt rt_adapt;
+typedef struct rt_adapt_report {
+  int32_t fbs;            /* frame buffers rendered for the tiles still active (= max n_t)       */
+  int32_t tiles_x, tiles_y, tiles_active;
+  int64_t pixels, pixels_active;
+  int64_t pixel_fbs;      /* sum over pixels of n_t: the work done; pixels x fbs without retiring */
+  int64_t pixels_above;   /* pixels with noise > threshold, each at its own tile's n_t           */
+  float threshold, max_noise;
+} rt_adapt_report;
+
+/* args as for rt_accum_create (fb_count ignored; band tilings accepted).  chunk_fbs >= 1: frame buffers
+ * per launch, chunk_fbs x owned_rows x width <= 2^31.  Every tile starts active with n_t = 0. */
+int rt_adapt_create(rt_ctx* ctx, const rt_render_args* args, int32_t chunk_fbs, rt_adapt** out);
+/* Renders the next `count` fb ids for the active tiles only (rt_render_tiles' launch, at most chunk_fbs
+ * per launch) and folds them in; the fold's traffic is the active tiles'.  counters (may be NULL)
+ * receives this call's totals.  With no active tile it renders nothing, zeroes counters and returns
+ * RT_OK.  RT_ERR_ARG, before anything is rendered, when fbs + count would exceed rt_noise's 32 768;
+ * RT_ERR_STATE after another rt_scene_upload. */
+int rt_adapt_add(rt_adapt* ad, int32_t count, rt_counters* counters);
+/* Needs fbs >= 2 (RT_ERR_STATE otherwise).  For every active tile: the per-pixel noise by rt_noise's
+ * definition with n = n_t (the same device code), and the tile retires when at most max_above (>= 0) of
+ * its pixels have noise > threshold.  Retiring is final: a retired tile is never rendered again and its
+ * n_t stays.  rep (may be NULL) describes the state after retiring; max_noise and pixels_above cover all
+ * tiles, retired ones at their frozen n_t.  Only maxima and integer counts are reduced. */
+int rt_adapt_retire(rt_adapt* ad, float threshold, int32_t max_above, rt_adapt_report* rep);
+/* rt_accum_image's conventions; quant(sum / n_t) per pixel.  RT_ERR_STATE before the first frame buffer. */
+int rt_adapt_image(rt_adapt* ad, uint8_t* out, int32_t png_order);
+/* n_t of every tile: host array of tiles_x x tiles_y. */
+int rt_adapt_counts(rt_adapt* ad, int32_t* tile_fbs);
+/* The per-pixel noise, each pixel at its tile's n_t: [owned_rows][width] floats, device or host pointer.
+ * Needs fbs >= 2. */
+int rt_adapt_noise_map(rt_adapt* ad, float* out);
+/* The report rt_adapt_retire would give, retiring nothing.  Needs fbs >= 2. */
+int rt_adapt_get_report(rt_adapt* ad, float threshold, rt_adapt_report* rep);
+/* Device time in ms of the last fold kernel (the last chunk of rt_adapt_add) and of the last
+ * rt_adapt_retire's measure kernel; 0 before one. */
+float rt_adapt_last_add_ms(const rt_adapt* ad);
+float rt_adapt_last_retire_ms(const rt_adapt* ad);
+int rt_adapt_destroy(rt_adapt* ad);
+
 /* ------------------------------------------------------------------ host scene library */
 /* Builds one of the reference scenes (scenes.h) on the host: "basic", "first", "big1" (alias
  * "random"), "two_spheres", "two_perlin", "cornell", "cornell_smoke", "triangle", "triangles",

@@ -12,6 +12,9 @@ Host mirror of the reference's interface for that path (names and argument meani
     previews, stop and resume through ``Context.accumulator`` / ``Accumulator`` / ``read_checkpoint``;
     ``until_noise=`` stops the draw once the per-pixel noise estimate of ``Accumulator.noise_monitor``
     (``NoiseMonitor``, ``read_noise``) says the 8-bit image has converged
+  * ``draw_adaptive(scene, settings, every=..., until_noise=...)`` — the same draw rendering only the
+    16 x 16 tiles that are still noisy (``Context.adaptive`` / ``AdaptiveAccumulator``,
+    ``Context.render_tiles``)
   * ``Context.render_init / render / resolve`` — the kernels render_init (render.h:84-92) and
     render (render.h:94-113) behind the C ABI of include/rt_hip.h
 
@@ -155,6 +158,19 @@ class rt_noise_report(ctypes.Structure):
         return d
 
 
+class rt_adapt_report(ctypes.Structure):
+    """include/rt_hip.h rt_adapt_report."""
+    _fields_ = [("fbs", c_int32), ("tiles_x", c_int32), ("tiles_y", c_int32), ("tiles_active", c_int32),
+                ("pixels", c_int64), ("pixels_active", c_int64), ("pixel_fbs", c_int64), ("pixels_above", c_int64),
+                ("threshold", c_float), ("max_noise", c_float)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_[:8]}
+        d["threshold"] = float(self.threshold)
+        d["max_noise"] = float(self.max_noise)
+        return d
+
+
 NOISE_MAX_FBS = 32768  # frame buffers a noise monitor accepts (include/rt_hip.h)
 
 # Every entry point of include/rt_hip.h: name -> (restype, argtypes)
@@ -201,6 +217,17 @@ ABI = {
     "rt_noise_blob_info": (c_int, [c_void_p, c_size_t, POINTER(rt_accum_info)]),
     "rt_noise_blob_pack": (c_int, [POINTER(rt_accum_info), c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]),
     "rt_noise_blob_measure": (c_int, [c_void_p, c_size_t, c_float, POINTER(rt_noise_report), c_void_p, c_void_p, c_void_p]),
+    "rt_render_tiles": (c_int, [c_void_p, POINTER(rt_render_args), c_void_p, c_int32, c_void_p, POINTER(rt_counters)]),
+    "rt_adapt_create": (c_int, [c_void_p, POINTER(rt_render_args), c_int32, POINTER(c_void_p)]),
+    "rt_adapt_add": (c_int, [c_void_p, c_int32, POINTER(rt_counters)]),
+    "rt_adapt_retire": (c_int, [c_void_p, c_float, c_int32, POINTER(rt_adapt_report)]),
+    "rt_adapt_image": (c_int, [c_void_p, c_void_p, c_int32]),
+    "rt_adapt_counts": (c_int, [c_void_p, c_void_p]),
+    "rt_adapt_noise_map": (c_int, [c_void_p, c_void_p]),
+    "rt_adapt_get_report": (c_int, [c_void_p, c_float, POINTER(rt_adapt_report)]),
+    "rt_adapt_last_add_ms": (c_float, [c_void_p]),
+    "rt_adapt_last_retire_ms": (c_float, [c_void_p]),
+    "rt_adapt_destroy": (c_int, [c_void_p]),
     "rt_scene_build": (c_int, [c_char_p, POINTER(c_void_p)]),
     "rt_scene_build_ex": (c_int, [c_char_p, c_void_p, POINTER(c_void_p)]),
     "rt_obj_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
@@ -432,6 +459,24 @@ class Context:
         self._check(lib().rt_render(self._c, ctypes.byref(args), c_void_p(fb_dev_ptr), ctypes.byref(cnt)),
                     "rt_render")
         return cnt.as_dict()
+
+    def render_tiles(self, args: rt_render_args, tiles, fb_dev_ptr: int) -> dict:
+        """rt_render_tiles: render() for the pixels of the listed 16 x 16 tiles only (the noise monitor's
+        tiles, id = ty * tiles_x + tx over (owned-row index, column)); every other float of the frame
+        buffer (a device or host address) stays as it is.  Returns the counters of the rendered items."""
+        self._after_torch()
+        t = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1)
+        cnt = rt_counters()
+        self._check(lib().rt_render_tiles(self._c, ctypes.byref(args), t.ctypes.data, len(t), c_void_p(fb_dev_ptr),
+                                          ctypes.byref(cnt)), "rt_render_tiles")
+        return cnt.as_dict()
+
+    def adaptive(self, args: rt_render_args, chunk_fbs: int = 1) -> "AdaptiveAccumulator":
+        """An adaptive progressive draw of args' configuration starting at args.fb_first (args.fb_count
+        is ignored): see AdaptiveAccumulator."""
+        h = c_void_p()
+        self._check(lib().rt_adapt_create(self._c, ctypes.byref(args), chunk_fbs, ctypes.byref(h)), "rt_adapt_create")
+        return AdaptiveAccumulator(self, h, args)
 
     def resolve(self, args: rt_render_args, fb_dev_ptr: int, out_dev_ptr: int) -> None:
         self._after_torch()
@@ -679,6 +724,80 @@ class NoiseMonitor:
             pass
 
 
+class AdaptiveAccumulator:
+    """rt_adapt of include/rt_hip.h: a progressive draw that renders only the 16 x 16 tiles that are
+    still noisy.  add() renders and folds in frame buffers for the active tiles, retire() stops every
+    active tile with at most max_above pixels above the threshold, for good.  Tile t of image() is
+    byte-identical to draw() with no_fb = counts()[t]."""
+
+    def __init__(self, ctx: Context, handle: c_void_p, args: rt_render_args):
+        import weakref
+
+        self.ctx = ctx
+        self._h = handle
+        self._rows, self._width = len(owned_rows(args)), args.width
+        if not hasattr(ctx, "_accums"):
+            ctx._accums = weakref.WeakSet()
+        ctx._accums.add(self)
+
+    def add(self, count: int = 1) -> dict:
+        """Render the next count frame buffers for the active tiles and fold them in; this call's counters."""
+        self.ctx._after_torch()
+        cnt = rt_counters()
+        self.ctx._check(lib().rt_adapt_add(self._h, count, ctypes.byref(cnt)), "rt_adapt_add")
+        return cnt.as_dict()
+
+    def retire(self, threshold: float, max_above: int = 0) -> dict:
+        """Retire the active tiles with at most max_above pixels of noise > threshold; the report after."""
+        rep = rt_adapt_report()
+        self.ctx._check(lib().rt_adapt_retire(self._h, threshold, max_above, ctypes.byref(rep)), "rt_adapt_retire")
+        return rep.as_dict()
+
+    def report(self, threshold: float) -> dict:
+        """retire()'s report without retiring anything."""
+        rep = rt_adapt_report()
+        self.ctx._check(lib().rt_adapt_get_report(self._h, threshold, ctypes.byref(rep)), "rt_adapt_get_report")
+        return rep.as_dict()
+
+    def image(self, png_order: bool = False) -> np.ndarray:
+        """(owned_rows, width, 3) uint8, owned rows ascending, or with png_order the whole image top row first."""
+        img = np.zeros((self._rows, self._width, 3), np.uint8)
+        self.ctx._check(lib().rt_adapt_image(self._h, img.ctypes.data, 1 if png_order else 0), "rt_adapt_image")
+        return img
+
+    def counts(self) -> np.ndarray:
+        """(tiles_y, tiles_x) int32: the frame buffers folded into every tile."""
+        out = np.zeros(((self._rows + 15) // 16, (self._width + 15) // 16), np.int32)
+        self.ctx._check(lib().rt_adapt_counts(self._h, out.ctypes.data), "rt_adapt_counts")
+        return out
+
+    def noise_map(self) -> np.ndarray:
+        """(owned_rows, width) float32: every pixel's noise at its own tile's frame-buffer count."""
+        out = np.zeros((self._rows, self._width), np.float32)
+        self.ctx._check(lib().rt_adapt_noise_map(self._h, out.ctypes.data), "rt_adapt_noise_map")
+        return out
+
+    def last_add_ms(self) -> float:
+        """Device time of the last fold kernel."""
+        return float(lib().rt_adapt_last_add_ms(self._h))
+
+    def last_retire_ms(self) -> float:
+        """Device time of the last retire()'s measure kernel."""
+        return float(lib().rt_adapt_last_retire_ms(self._h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_c", None):
+                lib().rt_adapt_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def read_noise(path: str, threshold: float) -> tuple[dict, np.ndarray, np.ndarray, np.ndarray]:
     """(report, tile_max, tile_above, map) of a monitor's side file, by the host-only rt_noise_blob_*
     functions (no context, no GPU); the report also carries the header's fields, as Accumulator.info()."""
@@ -798,6 +917,57 @@ def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context 
     finally:
         if acc is not None:
             acc.close()
+        if own:
+            ctx.close()
+
+
+def draw_adaptive(curr_scene: Scene, settings: render_settings, ctx: Context | None = None, every: int = 1,
+                  until_noise: float = 0.5, max_above: int = 0, min_fbs: int = 4, on_image=None, on_step=None,
+                  cam_mode: int = RT_CAM_REF_SLOT0, seed: int = 1984,
+                  chunk_fbs: int | None = None) -> tuple[np.ndarray, dict, np.ndarray]:
+    """draw() that stops rendering a 16 x 16 tile once at most max_above of its pixels have a noise
+    estimate above until_noise (8-bit output levels; NoiseMonitor's definition), and goes on with the
+    others.  Each step adds `every` frame buffers to the active tiles; from max(2, min_fbs) frame buffers
+    on it then retires tiles and calls on_step(report, done); on_image(image, done) gets the PNG-order
+    image after every step.  Ends when no tile is active or settings.no_fb is reached.  Returns (image,
+    counters of everything rendered, counts): tile t of the image is byte-identical to draw() with no_fb
+    = counts[t].  Stopping a tile on its own samples' spread biases it slightly towards stopping while it
+    happens to look smooth; min_fbs is the only guard."""
+    if settings.image_height <= 0:
+        settings.aspect_ratio = curr_scene.aspect
+        settings.calc_all()
+    if every < 1:
+        raise ValueError("every < 1")
+    if settings.no_fb > NOISE_MAX_FBS:
+        raise ValueError(f"an adaptive draw accepts at most {NOISE_MAX_FBS} frame buffers")
+    own = ctx is None
+    ctx = ctx or Context(0)
+    ad = None
+    try:
+        ctx.upload(curr_scene)
+        args = make_args(settings.image_width, settings.image_height, settings.samples_per_pixel_per_fb,
+                         0, 1, settings.max_depth, cam_mode, seed=seed)
+        ad = ctx.adaptive(args, chunk_fbs or every)
+        total = rt_counters().as_dict()
+        done, active, img = 0, True, None
+        while done < settings.no_fb and active:
+            n = min(every, settings.no_fb - done)
+            cnt = ad.add(n)
+            done += n
+            total = {k: total[k] + cnt[k] for k in total}
+            if done >= max(2, min_fbs):
+                report = ad.retire(until_noise, max_above)
+                active = report["tiles_active"] > 0
+                if on_step is not None:
+                    on_step(report, done)
+            if on_image is not None:
+                on_image(ad.image(png_order=True), done)
+        if ad is not None and done:
+            img = ad.image(png_order=True)
+        return img, total, ad.counts()
+    finally:
+        if ad is not None:
+            ad.close()
         if own:
             ctx.close()
 

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/rt_hip.h"
+#include "rt_tile_list.h"
 #include "rt_accum_blob.h"
 #include "rt_detmath.h"
 #include "rt_diag.h"
@@ -2790,32 +2791,28 @@ __global__ __launch_bounds__(kBlock) void accum_add_stats_kernel(const float* __
 // maximum and count come from the tile arrays in noise_reduce_kernel (one atomic per tile on one
 // address serialises: 32 400 tiles at 3840 x 2159 took longer than reading the moments).  No float is
 // summed anywhere: every output is independent of the order of reduction.
-__global__ __launch_bounds__(256) void noise_measure_kernel(const uint32_t* __restrict__ s1,
-                                                            const unsigned long long* __restrict__ s2, int n, int rows,
-                                                            int width, float threshold, float* __restrict__ map,
-                                                            float* __restrict__ tile_max, int32_t* __restrict__ tile_above) {
-  __shared__ float wave_max[4];
-  __shared__ int wave_above[4];
-  const int lane = threadIdx.x;
-  const int col = blockIdx.x * 16 + (lane & 15), row = blockIdx.y * 16 + (lane >> 4);
-  const bool valid = col < width && row < rows;
-  float noise = 0.0f;
-  if (valid) {
-    const long long px = (long long)row * width + col;
-    unsigned long long D = 0, S = 0;
+// (the per-pixel formula and the tile reduction are functions of their own: the adaptive accumulator's
+// adapt_measure_kernel runs the same device code with a per-tile n)
+__device__ __forceinline__ float pixel_noise(const uint32_t* __restrict__ s1, const unsigned long long* __restrict__ s2,
+                                             long long px, int n) {
+  unsigned long long D = 0, S = 0;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const unsigned long long m1 = s1[3 * px + j], m2 = s2[3 * px + j];
-      D += (unsigned long long)n * m2 - m1 * m1;
-      S += m1;
-    }
-    const double dn = (double)n, dn1 = (double)(n - 1);
-    const double a = (double)D / (3.0 * dn * dn * dn1 * 4228250625.0);
-    double m = (double)S / (3.0 * dn * 65025.0);
-    if (m < 0x1p-16) m = 0x1p-16;
-    noise = (float)(128.0 * __builtin_sqrt(a / m));
-    if (map) map[px] = noise;
+  for (int j = 0; j < 3; ++j) {
+    const unsigned long long m1 = s1[3 * px + j], m2 = s2[3 * px + j];
+    D += (unsigned long long)n * m2 - m1 * m1;
+    S += m1;
   }
+  const double dn = (double)n, dn1 = (double)(n - 1);
+  const double a = (double)D / (3.0 * dn * dn * dn1 * 4228250625.0);
+  double m = (double)S / (3.0 * dn * 65025.0);
+  if (m < 0x1p-16) m = 0x1p-16;
+  return (float)(128.0 * __builtin_sqrt(a / m));
+}
+// A 256-lane workgroup's maximum of noise and count of lanes with noise > threshold, into tile_max[tile]
+// and tile_above[tile] (wave_max, wave_above: 4 LDS words each).
+__device__ __forceinline__ void noise_tile_reduce(bool valid, float noise, float threshold, float* wave_max, int* wave_above,
+                                                  int tile, float* __restrict__ tile_max, int32_t* __restrict__ tile_above) {
+  const int lane = threadIdx.x;
   const unsigned long long hot = __ballot(valid && noise > threshold);
   float mx = noise;
 #pragma unroll
@@ -2829,10 +2826,27 @@ __global__ __launch_bounds__(256) void noise_measure_kernel(const uint32_t* __re
   if (lane == 0) {
     const float t = fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]));
     const int cnt = wave_above[0] + wave_above[1] + wave_above[2] + wave_above[3];
-    const int tile = blockIdx.y * gridDim.x + blockIdx.x;
     tile_max[tile] = t;
     tile_above[tile] = cnt;
   }
+}
+__global__ __launch_bounds__(256) void noise_measure_kernel(const uint32_t* __restrict__ s1,
+                                                            const unsigned long long* __restrict__ s2, int n, int rows,
+                                                            int width, float threshold, float* __restrict__ map,
+                                                            float* __restrict__ tile_max, int32_t* __restrict__ tile_above) {
+  __shared__ float wave_max[4];
+  __shared__ int wave_above[4];
+  const int lane = threadIdx.x;
+  const int col = blockIdx.x * 16 + (lane & 15), row = blockIdx.y * 16 + (lane >> 4);
+  const bool valid = col < width && row < rows;
+  float noise = 0.0f;
+  if (valid) {
+    const long long px = (long long)row * width + col;
+    noise = pixel_noise(s1, s2, px, n);
+    if (map) map[px] = noise;
+  }
+  noise_tile_reduce(valid, noise, threshold, wave_max, wave_above, blockIdx.y * gridDim.x + blockIdx.x, tile_max,
+                    tile_above);
 }
 
 // Image-wide maximum (as the bit pattern of the non-negative float, in the low word of totals[1]) and
@@ -2883,6 +2897,95 @@ __global__ __launch_bounds__(kBlock) void accum_image_kernel(const float* __rest
   }
   const long long k1 = k0 + 4 < n ? k0 + 4 : n;
   for (long long k = k0; k < k1; ++k) out[k] = (uint8_t)quant(sums[k] / d);
+}
+
+// ---- launches over a set of noise tiles (rt_render_tiles) and the adaptive accumulator (rt_adapt)
+// "Noise tile" here is always the noise monitor's tile of 16 x 16 pixels over (owned-row index, column)
+// (rtacc::kNoiseTile), never the 8 x 8 camera-ray tile of kTileShift.
+//
+// The item list of a launch over the listed noise tiles: RenderParams::perm for the render kernels, which
+// decode item = q * fb_count * W + f * W + i (row position q, frame buffer f, column i).  One 256-lane
+// workgroup per listed tile, one lane per pixel; ntile[k] = {tile id, base, row stride, fb stride}: pixel
+// (ly, lx) of the tile in frame buffer f goes to position base + ly * row stride + f * fb stride + lx.  The
+// host (tile_list_build) chooses the strides: tile-major (a tile's pixels of one fb in adjacent claims) or
+// row-major (ascending items), and guarantees that the positions are a permutation of 0 .. n_items - 1.
+__global__ __launch_bounds__(256) void tile_items_kernel(const uint4* __restrict__ ntile, int tiles_x, int rows, int width,
+                                                         int fb_count, uint32_t* __restrict__ perm) {
+  const uint4 d = ntile[blockIdx.x];
+  const int lane = threadIdx.x, lx = lane & 15, ly = lane >> 4;
+  const int col = (int)(d.x % (unsigned)tiles_x) * 16 + lx, row = (int)(d.x / (unsigned)tiles_x) * 16 + ly;
+  if (col >= width || row >= rows) return;
+  const unsigned long long first = (unsigned long long)row * fb_count * width + col;
+  const unsigned long long pos = (unsigned long long)d.y + (unsigned long long)ly * d.z + lx;
+  for (int f = 0; f < fb_count; ++f) perm[pos + (unsigned long long)f * d.w] = (uint32_t)(first + (unsigned long long)f * width);
+}
+
+// rt_adapt: the nfb frame buffers at fb folded into the listed (active) noise tiles' values: the float sum
+// by accum_add_kernel's operations in its order, S1 and S2 as accum_add_stats_kernel keeps them.  One
+// workgroup per listed tile: the traffic is the active tiles', not the image's.  A tile row is 16 pixels =
+// 48 consecutive values; the 256 lanes take the tile's 768 values in three passes, consecutive lanes on
+// consecutive values of a row (one lane per pixel, three values 12 bytes apart, measured 127.7 us at
+// 1200 x 800 x 10 fb against this layout's 48.6 us).
+__global__ __launch_bounds__(256) void adapt_fold_kernel(const uint4* __restrict__ ntile, int tiles_x, int rows, int width,
+                                                         const float* __restrict__ fb, long long per_fb, int nfb,
+                                                         float* __restrict__ sums, uint32_t* __restrict__ s1,
+                                                         unsigned long long* __restrict__ s2) {
+  const unsigned id = ntile[blockIdx.x].x;
+  const int row0 = (int)(id / (unsigned)tiles_x) * 16, v0 = (int)(id % (unsigned)tiles_x) * 48;  // first row, first value of a row
+#pragma unroll
+  for (int pass = 0; pass < 3; ++pass) {
+    const int v = pass * 256 + (int)threadIdx.x;
+    const int row = row0 + v / 48, vx = v0 + v % 48;
+    if (row >= rows || vx >= 3 * width) continue;
+    const long long k = (long long)row * width * 3 + vx;
+    float a = sums[k];
+    uint32_t m1 = s1[k];
+    unsigned long long m2 = s2[k];
+    for (int f = 0; f < nfb; ++f) {
+      const int c = quant(fb[(long long)f * per_fb + k]);
+      a += (float)(c * c) / (255.0f * 255.0f);
+      const uint32_t q = (uint32_t)(c * c);
+      m1 += q;
+      m2 += (unsigned long long)q * q;
+    }
+    sums[k] = a;
+    s1[k] = m1;
+    s2[k] = m2;
+  }
+}
+
+// rt_adapt: noise_measure_kernel over listed noise tiles (list null: over every tile, tile = blockIdx.x),
+// each with its own n = tile_n[tile] >= 2; same per-pixel code, same tile reduction.
+__global__ __launch_bounds__(256) void adapt_measure_kernel(const uint4* __restrict__ ntile, const int32_t* __restrict__ tile_n,
+                                                            const uint32_t* __restrict__ s1,
+                                                            const unsigned long long* __restrict__ s2, int tiles_x, int rows,
+                                                            int width, float threshold, float* __restrict__ map,
+                                                            float* __restrict__ tile_max, int32_t* __restrict__ tile_above) {
+  __shared__ float wave_max[4];
+  __shared__ int wave_above[4];
+  const int tile = ntile ? (int)ntile[blockIdx.x].x : (int)blockIdx.x;
+  const int lane = threadIdx.x;
+  const int col = (tile % tiles_x) * 16 + (lane & 15), row = (tile / tiles_x) * 16 + (lane >> 4);
+  const bool valid = col < width && row < rows;
+  float noise = 0.0f;
+  if (valid) {
+    const long long px = (long long)row * width + col;
+    noise = pixel_noise(s1, s2, px, tile_n[tile]);
+    if (map) map[px] = noise;
+  }
+  noise_tile_reduce(valid, noise, threshold, wave_max, wave_above, tile, tile_max, tile_above);
+}
+
+// rt_adapt: accum_image_kernel with the divisor of the pixel's noise tile, out = quant(sum / n_t); one lane
+// per pixel.
+__global__ __launch_bounds__(kBlock) void adapt_image_kernel(const float* __restrict__ sums, const int32_t* __restrict__ tile_n,
+                                                            int tiles_x, int rows, int width, uint8_t* __restrict__ out) {
+  const long long px = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (px >= (long long)rows * width) return;
+  const int row = (int)(px / width), col = (int)(px - (long long)row * width);
+  const float d = (float)tile_n[(row >> 4) * tiles_x + (col >> 4)];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) out[3 * px + j] = (uint8_t)quant(sums[3 * px + j] / d);
 }
 
 // Split items (render_step_kernel split_mode 2): the fb value of each of the first n_split items
@@ -4583,7 +4686,12 @@ bool device_ptr(const void* p) {
   }
   return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged || at.isManaged;
 }
-int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* counters);
+// A launch over a caller-built item list (rt_render_tiles): perm[0 .. n_items) are the items to render.
+struct TileLaunch {
+  const uint32_t* perm;
+  unsigned long long n_items;
+};
+int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* counters, const TileLaunch* tl = nullptr);
 }  // namespace
 
 int rt_render(rt_ctx* c, const rt_render_args* a, float* fb, rt_counters* counters) {
@@ -4605,7 +4713,11 @@ int rt_render(rt_ctx* c, const rt_render_args* a, float* fb, rt_counters* counte
 }
 
 namespace {
-int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* counters) {
+// tl (a tile launch): the launch claims tl's items in tl's order and is isolated from the context's
+// schedule state -- no schedule is read, built or recorded (perm_key, pending_key, the split state and
+// host_cost / cost_key stay as they are; the schedule flags have no effect), no probe, no split samples,
+// n_long = 0, no item or row costs, rows in ascending order (the row-map cache is kept up to date).
+int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* counters, const TileLaunch* tl) {
   int rc = RT_OK;
   if (!c->have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
   if (!c->states || c->states_n != (long long)a->width * a->height || c->states_seed != a->seed)
@@ -4630,7 +4742,7 @@ int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* c
   std::vector<int32_t> rm(2 * (size_t)rows);
   rt_owned_rows(a, rm.data());
   const long long key[5] = {c->scene_gen, a->width, a->height, a->spp, a->max_depth};
-  const bool have_cost = std::equal(key, key + 5, c->cost_key) && (int)c->host_cost.size() == a->height;
+  const bool have_cost = !tl && std::equal(key, key + 5, c->cost_key) && (int)c->host_cost.size() == a->height;
   for (int q = 0; q < rows; ++q) rm[rows + q] = q;
   // Costliest rows first only when lanes get few items each (a rank's share of a multi-GPU
   // image): there the launch ends with its last long item; with many items per lane bottom-to-top
@@ -4650,8 +4762,8 @@ int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* c
                              a->fb_count,  a->band_rows, a->band_first, a->band_stride, a->cam_mode};
   // (up to 2^31 items: 6 bytes of cost and position per item, C5's configured 100 fb x 100 spp draw
   // has 829 M; perm holds 32-bit positions)
-  const bool sched = items <= (1LL << 31) && (a->flags & RT_FLAG_NO_SCHEDULE) == 0;
-  if ((a->flags & RT_FLAG_FRESH) != 0) {  // as the configuration's first launch
+  const bool sched = !tl && items <= (1LL << 31) && (a->flags & RT_FLAG_NO_SCHEDULE) == 0;
+  if (!tl && (a->flags & RT_FLAG_FRESH) != 0) {  // as the configuration's first launch
     std::fill(c->perm_key, c->perm_key + K, -1LL);
     std::fill(c->pending_key, c->pending_key + K, -1LL);
     c->split_state = -1;
@@ -4694,7 +4806,7 @@ int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* c
   }
   HIPCHK(c, hipMemsetAsync(c->work, 0, 8 * sizeof(unsigned long long), c->stream));
   // row costs order the rows only when there is no item schedule: measured only then
-  const bool measure_rows = !have_cost && !sched;
+  const bool measure_rows = !tl && !have_cost && !sched;
   if (measure_rows) HIPCHK(c, hipMemsetAsync(c->row_cost, 0, (size_t)a->height * sizeof(unsigned long long), c->stream));
 
   RenderParams P{};
@@ -4705,7 +4817,7 @@ int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* c
   P.row_cost = measure_rows ? c->row_cost : nullptr;  // measured once per configuration
   P.work = c->work;
   P.counters = c->work + 1;
-  P.total_items = (unsigned long long)a->fb_count * rows * a->width;
+  P.total_items = tl ? tl->n_items : (unsigned long long)a->fb_count * rows * a->width;
   P.npix = (long long)a->width * a->height;
   P.W = a->width;
   P.H = a->height;
@@ -4768,7 +4880,7 @@ int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* c
   // (round 4, after the triangle dedupe and two steps per check, C4 Mrays/s at 40/48/52/56/60/62: 13 490 /
   // 13 922 / 14 052 / 14 090 / 13 932 / 13 618; C2 at 56/60/62: 14 659 / 14 747 / 14 605)
   P.shade_min = (kVariants[var].mask & F_TRI) != 0 ? kShadeMinMesh : kShadeMin;
-  P.perm = have_perm ? c->perm : nullptr;
+  P.perm = tl ? tl->perm : (have_perm ? c->perm : nullptr);
   P.n_long = have_perm ? c->n_long : 0;
   // Split samples of the longest items (stepwise kernel; scheduled launches of a configuration
   // with split items): the launch after the measuring one records their sample-start RNG states,
@@ -5085,7 +5197,8 @@ int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* c
   RT_WAVE_HOST_WRITE();
   RT_STEP_COUNT_HOST_PRINT(var);
   RT_STAMP_HOST_WRITE();
-  if (host_cnt[4] != (unsigned long long)a->spp * (unsigned long long)items)  // split samples: items != work items
+  // (split samples: items != work items)
+  if (host_cnt[4] != (unsigned long long)a->spp * (tl ? tl->n_items : (unsigned long long)items))
     return fail(c, RT_ERR_HIP, "render kernel did not complete every sample");
   return RT_OK;
 }
@@ -5693,6 +5806,422 @@ int rt_noise_load(rt_accum* acc, const void* blob, size_t n, rt_noise** out) {
   nm->fbs = info.args.fb_count;
   *out = nm;
   return RT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------- tile launches, adaptive accumulator
+// rt_render over a set of the noise monitor's tiles (16 x 16 pixels over (owned-row index, column)), and
+// the accumulator that stops rendering a tile once its own noise estimate is low enough (include/rt_hip.h).
+struct rt_adapt {
+  rt_ctx* ctx = nullptr;
+  rt_render_args args{};  // fb_count = frame buffers rendered for the tiles still active (max n_t)
+  int32_t chunk = 1;
+  long long per_fb = 0;  // owned_rows x width x 3
+  int rows = 0, tiles_x = 0, tiles_y = 0;
+  long long scene_gen = 0;
+  float* sums = nullptr;             // [per_fb]
+  uint32_t* s1 = nullptr;            // [per_fb] sum of c^2
+  unsigned long long* s2 = nullptr;  // [per_fb] sum of c^4
+  float* scratch = nullptr;          // [chunk][per_fb], allocated by the first rt_adapt_add
+  uint32_t* perm = nullptr;          // [chunk x owned pixels] item list of a tile launch, with scratch
+  uint4* ntile = nullptr;            // [tiles] the active noise tiles' list (tile_items_kernel's records)
+  int32_t* tile_n = nullptr;         // [tiles] n_t
+  float* tile_max = nullptr;         // [tiles] measure outputs
+  int32_t* tile_above = nullptr;
+  uint8_t* img = nullptr;            // [per_fb], allocated by the first rt_adapt_image into host memory
+  std::vector<int32_t> n_t;          // host copy of tile_n (kept alive for its upload)
+  std::vector<int32_t> active;       // ids of the active tiles, ascending
+  std::vector<rttile::Rec> ntile_host;     // what ntile holds (kept alive for its upload)
+  std::vector<float> h_max;          // host copies of the measure outputs; once have_measure, the retired
+  std::vector<int32_t> h_above;      // tiles' entries are current at threshold `measured` (theirs never change)
+  float measured = 0.0f;
+  bool have_measure = false;
+  // around the last fold (ev[0], ev[1]) and the last retire's measure kernel (ev[2], ev[3])
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool add_timed = false, retire_timed = false;
+};
+
+namespace {
+static_assert(rttile::kTile == rtacc::kNoiseTile, "tile launches use the noise monitor's tiles");
+inline void ntile_size(int id, int tiles_x, int rows, int width, int& tw, int& th) { rttile::size(id, tiles_x, rows, width, tw, th); }
+
+// The records uploaded to ntile_dev and expanded into perm_dev (both large enough), queued on the stream;
+// rec must stay alive until the stream has been synchronised (render_dev does).
+int tile_items(rt_ctx* c, const std::vector<rttile::Rec>& rec, int tiles_x, int rows, int width, int fb_count, uint4* ntile_dev,
+               uint32_t* perm_dev) {
+  HIPCHK(c, hipMemcpyAsync(ntile_dev, rec.data(), rec.size() * sizeof(uint4), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(tile_items_kernel, dim3((unsigned)rec.size()), dim3(256), 0, c->stream, ntile_dev, tiles_x, rows, width,
+                     fb_count, perm_dev);
+  HIPCHK(c, hipGetLastError());
+  return RT_OK;
+}
+
+void add_counters(rt_counters& t, const rt_counters& x) {
+  t.segments += x.segments;
+  t.node_tests += x.node_tests;
+  t.prim_tests += x.prim_tests;
+  t.samples += x.samples;
+  t.fallbacks += x.fallbacks;
+}
+
+// adapt_measure_kernel over the active tiles (all = false; the retired tiles' entries are re-measured too
+// when they hold the counts of another threshold) or every tile, then the tile arrays to the host:
+// afterwards h_max / h_above are current for every tile at `threshold`.  map_dev may be null.
+int adapt_measure(rt_adapt* ad, float threshold, bool all, float* map_dev, bool timed) {
+  rt_ctx* c = ad->ctx;
+  const size_t tiles = (size_t)ad->tiles_x * ad->tiles_y;
+  if (!ad->have_measure || memcmp(&ad->measured, &threshold, sizeof(float)) != 0) all = true;  // counts of another threshold
+  const unsigned blocks = all ? (unsigned)tiles : (unsigned)ad->active.size();
+  if (timed) HIPCHK(c, hipEventRecord(ad->ev[2], c->stream));
+  if (blocks > 0) {
+    hipLaunchKernelGGL(adapt_measure_kernel, dim3(blocks), dim3(256), 0, c->stream, all ? (const uint4*)nullptr : ad->ntile,
+                       ad->tile_n, ad->s1, ad->s2, ad->tiles_x, ad->rows, ad->args.width, threshold, map_dev, ad->tile_max,
+                       ad->tile_above);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (timed) {
+    HIPCHK(c, hipEventRecord(ad->ev[3], c->stream));
+    ad->retire_timed = true;
+  }
+  HIPCHK(c, hipMemcpyAsync(ad->h_max.data(), ad->tile_max, tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(ad->h_above.data(), ad->tile_above, tiles * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  ad->measured = threshold;
+  ad->have_measure = true;
+  return RT_OK;
+}
+
+// The active list as tile_items_kernel's records for launches of fb_count frame buffers, on the device.
+int adapt_list(rt_adapt* ad, int fb_count, unsigned long long* n_items) {
+  rt_ctx* c = ad->ctx;
+  *n_items = rttile::records(ad->active.data(), (int)ad->active.size(), ad->tiles_x, ad->rows, ad->args.width, fb_count,
+                          ad->ntile_host);
+  HIPCHK(c, hipMemcpyAsync(ad->ntile, ad->ntile_host.data(), ad->ntile_host.size() * sizeof(uint4), hipMemcpyHostToDevice,
+                           c->stream));
+  return RT_OK;
+}
+
+void adapt_report(const rt_adapt* ad, float threshold, rt_adapt_report* rep) {
+  const size_t tiles = (size_t)ad->tiles_x * ad->tiles_y;
+  rep->fbs = ad->args.fb_count;
+  rep->tiles_x = ad->tiles_x;
+  rep->tiles_y = ad->tiles_y;
+  rep->tiles_active = (int32_t)ad->active.size();
+  rep->pixels = (int64_t)ad->rows * ad->args.width;
+  rep->pixels_active = 0;
+  rep->pixel_fbs = 0;
+  rep->pixels_above = 0;
+  rep->threshold = threshold;
+  float mx = 0.0f;
+  for (size_t t = 0; t < tiles; ++t) {
+    int tw, th;
+    ntile_size((int)t, ad->tiles_x, ad->rows, ad->args.width, tw, th);
+    rep->pixel_fbs += (int64_t)tw * th * ad->n_t[t];
+    rep->pixels_above += ad->h_above[t];
+    mx = std::max(mx, ad->h_max[t]);
+  }
+  for (int32_t t : ad->active) {
+    int tw, th;
+    ntile_size(t, ad->tiles_x, ad->rows, ad->args.width, tw, th);
+    rep->pixels_active += (int64_t)tw * th;
+  }
+  rep->max_noise = mx;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_tiles(rt_ctx* c, const rt_render_args* a, const int32_t* tiles, int32_t n_tiles, float* fb,
+                    rt_counters* counters) {
+  if (!c) return RT_ERR_ARG;
+  int rc = validate_args(c, a);
+  if (rc) return rc;
+  if (!fb) return fail(c, RT_ERR_ARG, "null fb");
+  if (!tiles || n_tiles <= 0) return fail(c, RT_ERR_ARG, "empty tile list");
+  const int rows = rt_owned_rows(a, nullptr);
+  if (rows <= 0) return fail(c, RT_ERR_ARG, "no rows owned");
+  const long long items = (long long)a->fb_count * rows * a->width;
+  if (items > (1LL << 31)) return fail(c, RT_ERR_ARG, "tile launch: more than 2^31 items (fb_count x owned rows x width)");
+  const int tiles_x = (a->width + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
+  const int tiles_y = (rows + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
+  const long long n_all = (long long)tiles_x * tiles_y;
+  if (n_tiles > n_all) return fail(c, RT_ERR_ARG, "tile list: a repeated tile id");
+  std::vector<uint8_t> seen((size_t)n_all, 0);
+  for (int k = 0; k < n_tiles; ++k) {
+    if (tiles[k] < 0 || tiles[k] >= n_all) return fail(c, RT_ERR_ARG, "tile list: id out of range");
+    if (seen[(size_t)tiles[k]]) return fail(c, RT_ERR_ARG, "tile list: a repeated tile id");
+    seen[(size_t)tiles[k]] = 1;
+  }
+  if (!c->have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
+  if (!c->states || c->states_n != (long long)a->width * a->height || c->states_seed != a->seed)
+    return fail(c, RT_ERR_STATE, "rt_render_init not called for this size/seed");
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<rttile::Rec> rec;
+  TileLaunch tl{nullptr, rttile::records(tiles, n_tiles, tiles_x, rows, a->width, a->fb_count, rec)};
+  uint4* ntile = nullptr;
+  uint32_t* perm = nullptr;
+  float* tmp = nullptr;  // a host fb is staged in and out: the floats outside the listed tiles stay
+  const size_t fb_bytes = (size_t)items * 3 * sizeof(float);
+  const bool host_fb = !device_ptr(fb);
+  if (hipMalloc((void**)&ntile, rec.size() * sizeof(uint4)) != hipSuccess ||
+      hipMalloc((void**)&perm, (size_t)tl.n_items * sizeof(uint32_t)) != hipSuccess ||
+      (host_fb && hipMalloc((void**)&tmp, fb_bytes) != hipSuccess)) {
+    (void)hipGetLastError();
+    rc = fail(c, RT_ERR_NOMEM, "hipMalloc tile launch");
+  }
+  if (!rc && host_fb && hipMemcpy(tmp, fb, fb_bytes, hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(c, RT_ERR_HIP, "copy frame buffer to device");
+  if (!rc) rc = tile_items(c, rec, tiles_x, rows, a->width, a->fb_count, ntile, perm);
+  tl.perm = perm;
+  if (!rc) rc = render_dev(c, a, host_fb ? tmp : fb, counters, &tl);
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(c, RT_ERR_HIP, "tile launch");
+  if (!rc && host_fb && hipMemcpy(fb, tmp, fb_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(c, RT_ERR_HIP, "copy frame buffer to host");
+  if (ntile) (void)hipFree(ntile);
+  if (perm) (void)hipFree(perm);
+  if (tmp) (void)hipFree(tmp);
+  return rc;
+}
+
+int rt_adapt_destroy(rt_adapt* ad) {
+  if (!ad) return RT_ERR_ARG;
+  (void)hipSetDevice(ad->ctx->device);
+  (void)hipStreamSynchronize(ad->ctx->stream);
+  void* bufs[] = {ad->sums, ad->s1, ad->s2, ad->scratch, ad->perm, ad->ntile, ad->tile_n, ad->tile_max, ad->tile_above, ad->img};
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
+  for (hipEvent_t e : ad->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete ad;
+  return RT_OK;
+}
+
+int rt_adapt_create(rt_ctx* c, const rt_render_args* a, int32_t chunk_fbs, rt_adapt** out) {
+  if (!c) return RT_ERR_ARG;
+  if (!out) return fail(c, RT_ERR_ARG, "null adaptive accumulator pointer");
+  *out = nullptr;
+  if (!a) return fail(c, RT_ERR_ARG, "null args");
+  rt_render_args one = *a;
+  one.fb_count = 1;
+  const int rc = validate_args(c, &one);
+  if (rc) return rc;
+  if (chunk_fbs < 1) return fail(c, RT_ERR_ARG, "chunk_fbs < 1");
+  if (a->fb_first > INT32_MAX - chunk_fbs) return fail(c, RT_ERR_ARG, "fb range overflows");
+  const long long rows = rt_owned_rows(a, nullptr);
+  const long long per_fb = rows * a->width * 3;
+  if (per_fb <= 0) return fail(c, RT_ERR_ARG, "no rows owned");
+  if ((long long)chunk_fbs * rows * a->width > (1LL << 31)) return fail(c, RT_ERR_ARG, "chunk_fbs x owned rows x width > 2^31");
+  const long long tiles_x = (a->width + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
+  const long long tiles_y = (rows + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
+  if (tiles_x * tiles_y > INT32_MAX) return fail(c, RT_ERR_ARG, "adaptive accumulator: too many tiles");
+  if (!c->have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
+  HIPCHK(c, hipSetDevice(c->device));
+  rt_adapt* ad = new rt_adapt;
+  ad->ctx = c;
+  ad->args = *a;
+  ad->args.fb_count = 0;
+  ad->chunk = chunk_fbs;
+  ad->per_fb = per_fb;
+  ad->rows = (int)rows;
+  ad->tiles_x = (int)tiles_x;
+  ad->tiles_y = (int)tiles_y;
+  ad->scene_gen = c->scene_gen;
+  const size_t nv = (size_t)per_fb, tiles = (size_t)(tiles_x * tiles_y);
+  ad->n_t.assign(tiles, 0);
+  ad->h_max.assign(tiles, 0.0f);
+  ad->h_above.assign(tiles, 0);
+  ad->active.resize(tiles);
+  for (size_t t = 0; t < tiles; ++t) ad->active[t] = (int32_t)t;
+  bool ok = hipMalloc((void**)&ad->sums, nv * sizeof(float)) == hipSuccess;
+  ok = ok && hipMalloc((void**)&ad->s1, nv * sizeof(uint32_t)) == hipSuccess;
+  ok = ok && hipMalloc((void**)&ad->s2, nv * sizeof(unsigned long long)) == hipSuccess;
+  ok = ok && hipMalloc((void**)&ad->ntile, tiles * sizeof(uint4)) == hipSuccess;
+  ok = ok && hipMalloc((void**)&ad->tile_n, tiles * sizeof(int32_t)) == hipSuccess;
+  ok = ok && hipMalloc((void**)&ad->tile_max, tiles * sizeof(float)) == hipSuccess;
+  ok = ok && hipMalloc((void**)&ad->tile_above, tiles * sizeof(int32_t)) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    rt_adapt_destroy(ad);
+    return fail(c, RT_ERR_NOMEM, "hipMalloc adaptive accumulator");
+  }
+  for (hipEvent_t& e : ad->ev)
+    if (ok && hipEventCreate(&e) != hipSuccess) {
+      e = nullptr;
+      ok = false;
+    }
+  ok = ok && hipMemsetAsync(ad->sums, 0, nv * sizeof(float), c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(ad->s1, 0, nv * sizeof(uint32_t), c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(ad->s2, 0, nv * sizeof(unsigned long long), c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(ad->tile_n, 0, tiles * sizeof(int32_t), c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(ad->tile_max, 0, tiles * sizeof(float), c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(ad->tile_above, 0, tiles * sizeof(int32_t), c->stream) == hipSuccess;
+  if (!ok) {
+    rt_adapt_destroy(ad);
+    return fail(c, RT_ERR_HIP, "set up adaptive accumulator");
+  }
+  *out = ad;
+  return RT_OK;
+}
+
+int rt_adapt_add(rt_adapt* ad, int32_t count, rt_counters* counters) {
+  if (!ad) return RT_ERR_ARG;
+  rt_ctx* c = ad->ctx;
+  rt_render_args& a = ad->args;
+  if (count < 1) return fail(c, RT_ERR_ARG, "count < 1");
+  if (count > INT32_MAX - a.fb_first - a.fb_count) return fail(c, RT_ERR_ARG, "fb range overflows");
+  if (count > rtacc::kNoiseMaxFbs - a.fb_count) return fail(c, RT_ERR_ARG, "noise monitor: more than 32768 frame buffers");
+  if (ad->scene_gen != c->scene_gen) return fail(c, RT_ERR_STATE, "scene uploaded again since the accumulator was created");
+  rt_counters total = {};
+  if (ad->active.empty()) {  // every tile has retired: nothing is rendered
+    if (counters) *counters = total;
+    return RT_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->states || c->states_n != (long long)a.width * a.height || c->states_seed != a.seed) {
+    const int rc = rt_render_init(c, a.width, a.height, a.seed);
+    if (rc) return rc;
+  }
+  if (!ad->scratch) {
+    const size_t px = (size_t)ad->chunk * ad->rows * a.width;
+    if (hipMalloc((void**)&ad->scratch, px * 3 * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&ad->perm, px * sizeof(uint32_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      if (ad->scratch) (void)hipFree(ad->scratch);
+      ad->scratch = nullptr;
+      return fail(c, RT_ERR_NOMEM, "hipMalloc adaptive frame buffers");
+    }
+  }
+  for (int32_t left = count; left > 0;) {
+    const int32_t n = std::min(left, ad->chunk);
+    rt_render_args r = a;
+    r.fb_first = a.fb_first + a.fb_count;
+    r.fb_count = n;
+    TileLaunch tl{ad->perm, 0};
+    int rc = adapt_list(ad, n, &tl.n_items);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tile_items_kernel, dim3((unsigned)ad->active.size()), dim3(256), 0, c->stream, ad->ntile, ad->tiles_x,
+                       ad->rows, a.width, n, ad->perm);
+    HIPCHK(c, hipGetLastError());
+    rt_counters cnt = {};
+    if ((rc = render_dev(c, &r, ad->scratch, &cnt, &tl))) return rc;
+    HIPCHK(c, hipEventRecord(ad->ev[0], c->stream));
+    hipLaunchKernelGGL(adapt_fold_kernel, dim3((unsigned)ad->active.size()), dim3(256), 0, c->stream, ad->ntile, ad->tiles_x,
+                       ad->rows, a.width, ad->scratch, ad->per_fb, n, ad->sums, ad->s1, ad->s2);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ad->ev[1], c->stream));
+    ad->add_timed = true;
+    a.fb_count += n;
+    add_counters(total, cnt);
+    left -= n;
+  }
+  for (int32_t t : ad->active) ad->n_t[(size_t)t] = a.fb_count;
+  HIPCHK(c, hipMemcpyAsync(ad->tile_n, ad->n_t.data(), ad->n_t.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (counters) *counters = total;
+  return RT_OK;
+}
+
+int rt_adapt_retire(rt_adapt* ad, float threshold, int32_t max_above, rt_adapt_report* rep) {
+  if (!ad) return RT_ERR_ARG;
+  rt_ctx* c = ad->ctx;
+  if (max_above < 0) return fail(c, RT_ERR_ARG, "max_above < 0");
+  if (ad->args.fb_count < 2) return fail(c, RT_ERR_STATE, "noise needs at least 2 frame buffers");
+  HIPCHK(c, hipSetDevice(c->device));
+  unsigned long long unused = 0;
+  int rc = adapt_list(ad, 1, &unused);  // the measure kernel reads the ids only
+  if (!rc) rc = adapt_measure(ad, threshold, false, nullptr, true);
+  if (rc) return rc;
+  std::vector<int32_t> keep;
+  for (int32_t t : ad->active)
+    if (ad->h_above[(size_t)t] > max_above) keep.push_back(t);
+  ad->active.swap(keep);  // retiring is final: n_t of the others stays at fbs
+  if (rep) adapt_report(ad, threshold, rep);
+  return RT_OK;
+}
+
+int rt_adapt_get_report(rt_adapt* ad, float threshold, rt_adapt_report* rep) {
+  if (!ad) return RT_ERR_ARG;
+  rt_ctx* c = ad->ctx;
+  if (!rep) return fail(c, RT_ERR_ARG, "null report");
+  if (ad->args.fb_count < 2) return fail(c, RT_ERR_STATE, "noise needs at least 2 frame buffers");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = adapt_measure(ad, threshold, true, nullptr, false);
+  if (rc) return rc;
+  adapt_report(ad, threshold, rep);
+  return RT_OK;
+}
+
+int rt_adapt_counts(rt_adapt* ad, int32_t* tile_fbs) {
+  if (!ad) return RT_ERR_ARG;
+  if (!tile_fbs) return fail(ad->ctx, RT_ERR_ARG, "null counts");
+  std::copy(ad->n_t.begin(), ad->n_t.end(), tile_fbs);
+  return RT_OK;
+}
+
+int rt_adapt_noise_map(rt_adapt* ad, float* out) {
+  if (!ad) return RT_ERR_ARG;
+  rt_ctx* c = ad->ctx;
+  if (!out) return fail(c, RT_ERR_ARG, "null map");
+  if (ad->args.fb_count < 2) return fail(c, RT_ERR_STATE, "noise needs at least 2 frame buffers");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)ad->rows * ad->args.width * sizeof(float);
+  float* tmp = nullptr;  // a host map is staged through device memory
+  if (!device_ptr(out) && hipMalloc((void**)&tmp, bytes) != hipSuccess) return fail(c, RT_ERR_NOMEM, "hipMalloc noise map");
+  int rc = adapt_measure(ad, ad->have_measure ? ad->measured : 0.0f, true, tmp ? tmp : out, false);
+  if (!rc && tmp && hipMemcpy(out, tmp, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(c, RT_ERR_HIP, "copy noise map");
+  if (tmp) (void)hipFree(tmp);
+  return rc;
+}
+
+int rt_adapt_image(rt_adapt* ad, uint8_t* out, int32_t png_order) {
+  if (!ad) return RT_ERR_ARG;
+  rt_ctx* c = ad->ctx;
+  if (!out) return fail(c, RT_ERR_ARG, "null image");
+  if (png_order != 0 && png_order != 1) return fail(c, RT_ERR_ARG, "bad png_order");
+  const rt_render_args& a = ad->args;
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool out_dev = device_ptr(out);
+  if (png_order && ad->per_fb != (long long)a.width * a.height * 3)
+    return fail(c, RT_ERR_ARG, "png_order needs the whole-image tiling");
+  if (png_order && out_dev) return fail(c, RT_ERR_ARG, "png_order needs a host image");
+  if (a.fb_count < 1) return fail(c, RT_ERR_STATE, "no frame buffer accumulated yet");
+  if (!out_dev && !ad->img && hipMalloc((void**)&ad->img, (size_t)ad->per_fb) != hipSuccess) {
+    ad->img = nullptr;
+    return fail(c, RT_ERR_NOMEM, "hipMalloc adaptive image");
+  }
+  uint8_t* img = out_dev ? out : ad->img;
+  const long long px = ad->per_fb / 3;
+  hipLaunchKernelGGL(adapt_image_kernel, dim3((unsigned)((px + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, ad->sums,
+                     ad->tile_n, ad->tiles_x, ad->rows, a.width, img);
+  HIPCHK(c, hipGetLastError());
+  if (out_dev) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+  }
+  if (!png_order) {
+    HIPCHK(c, hipMemcpyAsync(out, img, (size_t)ad->per_fb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+  }
+  std::vector<uint8_t> tmp((size_t)ad->per_fb);
+  HIPCHK(c, hipMemcpyAsync(tmp.data(), img, tmp.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t row = (size_t)a.width * 3;
+  for (int j = 0; j < a.height; ++j) memcpy(out + (size_t)(a.height - 1 - j) * row, tmp.data() + j * row, row);
+  return RT_OK;
+}
+
+float rt_adapt_last_add_ms(const rt_adapt* ad) {
+  float ms = 0.0f;
+  if (!ad || !ad->add_timed || hipEventElapsedTime(&ms, ad->ev[0], ad->ev[1]) != hipSuccess) return 0.0f;
+  return ms;
+}
+float rt_adapt_last_retire_ms(const rt_adapt* ad) {
+  float ms = 0.0f;
+  if (!ad || !ad->retire_timed || hipEventElapsedTime(&ms, ad->ev[2], ad->ev[3]) != hipSuccess) return 0.0f;
+  return ms;
 }
 
 }  // extern "C"
