@@ -3,8 +3,8 @@
 // The product library (raytracing_gpu_amd/_build.py) defines nothing here: every hook below is an
 // empty macro, the kernels carry no timing code and the library reads no environment variable.
 // A diagnostic build sets -DRT_DIAG=<bits> (scripts/build_ab.sh NAME src -DRT_DIAG=...):
-//   1  per-wave counts of traversal-loop iterations, lane steps, shading phases and loop trips
-//      (printed to stderr after each launch)
+//   1  per-wave counts of traversal-loop iterations, lane steps, shading phases, loop trips and the
+//      traversal's leaf passes with their lanes (printed to stderr after each launch)
 //   2  per-wave cycle shares of the loop's phases: s_memtime stamps, appended to $RT_STAMPS_OUT
 //      (scripts/diag_stamps.py)
 //   4  per-wave start / work-exhausted / end times (s_memrealtime), written to $RT_WAVE_TIMES_OUT
@@ -21,31 +21,36 @@
 
 // ---------------------------------------------------------------- 1: step counts
 #if RT_DIAG & 1
-__device__ unsigned long long rt_diag_steps[4];
-__shared__ unsigned long long rt_diag_steps_acc[16][4];
+// 0 traversal-loop iterations, 1 lanes stepping in them, 2 shading phases, 3 loop trips,
+// 4 / 5 leaf passes entered first (a step's first pass, or the first pass of a vote) and the lanes
+// testing a leaf in them, 6 / 7 the same for the passes that follow it (a lane's second leaf)
+constexpr int kStepCounts = 8;
+__device__ unsigned long long rt_diag_steps[kStepCounts];
+__shared__ unsigned long long rt_diag_steps_acc[16][kStepCounts];
 __device__ __forceinline__ void rt_step_count(int k) {  // one count per wave (first active lane)
   const unsigned long long act = __ballot(1);
   if ((int)__lane_id() == __ffsll((long long)act) - 1) {
     rt_diag_steps_acc[threadIdx.x >> 6][k] += 1;
-    if (k == 0) rt_diag_steps_acc[threadIdx.x >> 6][1] += __popcll(act);
+    if (k == 0 || k == 4 || k == 6) rt_diag_steps_acc[threadIdx.x >> 6][k + 1] += __popcll(act);
   }
 }
 #define RT_STEP_COUNT(k) rt_step_count(k)
 #define RT_STEP_COUNT_BEGIN() \
-  if (__lane_id() < 4) rt_diag_steps_acc[threadIdx.x >> 6][__lane_id()] = 0
+  if (__lane_id() < kStepCounts) rt_diag_steps_acc[threadIdx.x >> 6][__lane_id()] = 0
 #define RT_STEP_COUNT_END() \
-  if (__lane_id() < 4) atomicAdd(&rt_diag_steps[__lane_id()], rt_diag_steps_acc[threadIdx.x >> 6][__lane_id()])
+  if (__lane_id() < kStepCounts) atomicAdd(&rt_diag_steps[__lane_id()], rt_diag_steps_acc[threadIdx.x >> 6][__lane_id()])
 #define RT_STEP_COUNT_HOST_RESET()                                   \
   do {                                                               \
-    const unsigned long long z_[4] = {0, 0, 0, 0};                   \
+    const unsigned long long z_[kStepCounts] = {};                   \
     (void)hipMemcpyToSymbol(HIP_SYMBOL(rt_diag_steps), z_, sizeof(z_)); \
   } while (0)
 #define RT_STEP_COUNT_HOST_PRINT(var)                                                                       \
   do {                                                                                                      \
-    unsigned long long h_[4];                                                                               \
+    unsigned long long h_[kStepCounts];                                                                     \
     (void)hipMemcpyFromSymbol(h_, HIP_SYMBOL(rt_diag_steps), sizeof(h_));                                   \
-    fprintf(stderr, "RT_STEP_DIAG var=%d trav_wave_iters=%llu trav_lane_steps=%llu shade_phases=%llu trips=%llu\n", \
-            var, h_[0], h_[1], h_[2], h_[3]);                                                               \
+    fprintf(stderr, "RT_STEP_DIAG var=%d trav_wave_iters=%llu trav_lane_steps=%llu shade_phases=%llu trips=%llu" \
+            " leaf_first=%llu leaf_first_lanes=%llu leaf_more=%llu leaf_more_lanes=%llu\n",                 \
+            var, h_[0], h_[1], h_[2], h_[3], h_[4], h_[5], h_[6], h_[7]);                                    \
   } while (0)
 #else
 #define RT_STEP_COUNT(k)

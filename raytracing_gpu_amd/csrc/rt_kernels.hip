@@ -883,6 +883,7 @@ __device__ __forceinline__ bool trav_step(const DScene& S, int fb, const Ray& r,
     for (int pass = 0; pass < 2; ++pass) {
       const int ch = pass == 0 ? p0 : p1;
       if (ch < 0) {
+        RT_STEP_COUNT(4 + 2 * pass);
         RT_STAMP(4);
         const int pi = -ch - 1;
         if constexpr ((F & F_WORLD) != 0) {
@@ -930,6 +931,151 @@ __device__ __forceinline__ bool trav_step(const DScene& S, int fb, const Ray& r,
   if (sp == 0) return false;
   cur = stk[BS * --sp];
   return true;
+}
+
+// Deferred leaf pass of render_step_kernel.  trav_step's pass runs in two steps of three for the
+// ~9 lanes whose pair just yielded a hit leaf.  Nothing in the search needs a leaf
+// tested in the step that found it: the decision uses only the hit inner children, candidates do
+// not depend on their order (take_candidate), and the cut only ever shrinks, so a box tested
+// against a stale cut is at worst visited for nothing -- a primitive in a box entered beyond
+// bhi (1 + 2^-8) has lo > bhi and changes neither the winner nor `second > bhi`.  So a lane carries
+// its hit leaf along (one child word, `pend`; 0: none) and the wave tests the leaves of all its
+// lanes together: when a lane holds more than the one it has room for, when leaf_pass_min(F) lanes
+// hold one, and before every shading phase.
+// leaf_pass_min: 0 = the variant tests its leaves in the step that finds them (trav_step);
+// above 64 = the count never fires and the vote is one ballot per step (measured fastest on C2:
+// every counting threshold lost more to the second ballot than its fuller passes gained).
+// The triangle-mesh variants gain as well (C4 -2.6 % at 65, -3.2 % at 16) but spill two more VGPRs
+// at the 128 cap, so they keep the immediate pass.
+#ifndef RT_LEAF_MIN
+#define RT_LEAF_MIN 65
+#endif
+#ifndef RT_LEAF_MIN_TRI
+#define RT_LEAF_MIN_TRI 0
+#endif
+constexpr int leaf_pass_min(int F) {
+  return (F & F_STEP) == 0 || (F & F_WORLD) != 0 ? 0 : ((F & F_TRI) != 0 ? RT_LEAF_MIN_TRI : RT_LEAF_MIN);
+}
+
+// The step's parts for the deferring variants (the same operations as trav_step's, in its order).
+// Node part: the pair `cur` tested against [tmin, min(bhi (1 + 2^-8), tmax)].
+template <int F>
+__device__ __forceinline__ void trav_pair(const DScene& S, int fb, V oi, V finv, float tmin, float tmax, float bhi,
+                                          int cur, bool& hl, bool& hr, float& tl, float& tr, int& c0, int& c1,
+                                          unsigned& nnode) {
+  RT_STAMP(3);
+  if constexpr ((F & F_STATS) != 0) nnode += 2;
+  const float cut = __builtin_fminf(bhi * 1.00390625f, tmax);
+  if constexpr ((F & F_QLDS) != 0) {
+    qpair(S, cur, oi, finv, tmin, cut, hl, hr, tl, tr, c0, c1);
+  } else {
+    float4 l0, l1, r0, r1;
+    if constexpr (planes<F>()) {  // the four planes of the staged tree (stage_lds)
+      const float4* n = nodes_of<F>(S) + 2 * fb + cur;
+      l0 = n[0];
+      l1 = n[kPlanePairs];
+      r0 = n[2 * kPlanePairs];
+      r1 = n[3 * kPlanePairs];
+    } else {
+      const float4* n = nodes_of<F>(S) + 2 * (fb + 2 * cur);
+      l0 = n[0];
+      l1 = n[1];
+      r0 = n[2];
+      r1 = n[3];
+    }
+    hl = fbox(l0, l1, oi, finv, tmin, cut, tl);
+    hr = fbox(r0, r1, oi, finv, tmin, cut, tr);
+    c0 = __float_as_int(l0.w);
+    c1 = __float_as_int(l1.w);
+  }
+}
+
+// Leaf part: the primitive of the child word ch < 0, as a candidate of the culled search.
+template <int F>
+__device__ __forceinline__ void trav_leaf(const DScene& S, int ch, const Ray& r, float a, float rcpa, float tmin,
+                                          float tmax, float& blo, float& bhi, float& second, int& best_prim,
+                                          int& best_rank, unsigned& nprim) {
+  static_assert((F & F_WORLD) == 0, "world-tree leaves are tested in trav_step");
+  RT_STAMP(4);
+  const int pi = -ch - 1;
+  const PrimRec q = load_prim<F>(S, pi);
+  float lo, hi;
+  if (prim_range<F>(S, q, r, a, rcpa, tmin, tmax, lo, hi, nprim))
+    take_candidate(lo, hi, pi, __float_as_int(q.c.y), blo, bhi, second, best_prim, best_rank);
+  RT_STAMP(3);
+}
+
+// Decision part: descend into the nearer hit child and push the other, else pop; false when the
+// search has ended.  hl / hr are the hit INNER children (hit leaves already cleared by the caller).
+template <int F>
+__device__ __forceinline__ bool trav_next(const DScene& S, bool hl, bool hr, float tl, float tr, int c0, int c1,
+                                          int& cur, int& sp, bool& overflow) {
+  stack_t<F>* stk = stack_of<F>(S);
+  constexpr int BS = render_block<F>();
+  if (hl && hr) {
+    const bool right_first = tr < tl;
+    if (sp < kStackDepth) stk[BS * sp++] = (stack_t<F>)(right_first ? c0 : c1);
+    else overflow = true;
+    cur = right_first ? c1 : c0;
+    return true;
+  }
+  if (hl || hr) {
+    cur = hl ? c0 : c1;
+    return true;
+  }
+  if (sp == 0) return false;
+  cur = stk[BS * --sp];
+  return true;
+}
+
+// Node part of a deferring step: the pair, the decision, and the hit leaf children in n0 / n1
+// (child words, 0: none) instead of their tests.
+template <int F>
+__device__ __forceinline__ bool trav_node(const DScene& S, int fb, V oi, V finv, float tmin, float tmax, float bhi,
+                                          int& cur, int& sp, bool& overflow, unsigned& nnode, int& n0, int& n1) {
+  float tl, tr;
+  bool hl, hr;
+  int c0, c1;
+  trav_pair<F>(S, fb, oi, finv, tmin, tmax, bhi, cur, hl, hr, tl, tr, c0, c1, nnode);
+  const bool la = hl && c0 < 0, lb = hr && c1 < 0;
+  n0 = la ? c0 : (lb ? c1 : 0);
+  n1 = (la && lb) ? c1 : 0;
+  if (la) hl = false;
+  if (lb) hr = false;
+  return trav_next<F>(S, hl, hr, tl, tr, c0, c1, cur, sp, overflow);
+}
+
+// The wave's vote after the node part (every lane of the wave, traversing or not; n0 = n1 = 0 for a
+// lane that did not step): a lane holds pend, n0, n1 in that order.  The pass runs when a lane holds
+// more than one leaf or leaf_pass_min(F) lanes hold one; every holding lane tests its first, and the
+// pass repeats while a lane still holds more than one.  What is left becomes the lane's pend.
+// `flush` (before a shading phase, n0 = n1 = 0): the pass runs when any lane holds a leaf, and no
+// lane keeps one.
+template <int F>
+__device__ __forceinline__ void leaf_vote(const DScene& S, bool flush, int& pend, int n0, int n1, const Ray& r,
+                                          float a, float rcpa, float tmin, float tmax, float& blo, float& bhi,
+                                          float& second, int& best_prim, int& best_rank, unsigned& nprim) {
+  constexpr int kMin = leaf_pass_min(F);
+  int q0 = pend, q1 = n0, q2 = n1;
+  if (q0 == 0) {
+    q0 = q1;
+    q1 = q2;
+    q2 = 0;
+  }
+  bool run = __ballot(q1 != 0) != 0;
+  if (kMin <= 64) run = run || __popcll(__ballot(q0 != 0)) >= (flush ? 1 : kMin);
+  else run = run || (flush && __ballot(q0 != 0) != 0);
+  for (int pass = 0; run; pass = 1) {
+    if (q0 != 0) {
+      RT_STEP_COUNT(pass == 0 ? 4 : 6);
+      trav_leaf<F>(S, q0, r, a, rcpa, tmin, tmax, blo, bhi, second, best_prim, best_rank, nprim);
+    }
+    q0 = q1;
+    q1 = q2;
+    q2 = 0;
+    run = __ballot((flush ? q0 : q1) != 0) != 0;
+  }
+  pend = q0;
 }
 
 // Camera-ray candidates of a world BVH from the per-tile candidate list (bin_tiles_kernel): every
@@ -2261,6 +2407,7 @@ void render_step_kernel(const RenderParams P) {
   Ray ray{};
   V finv = mk(0, 0, 0), oi = mk(0, 0, 0);
   int cur = 0, sp = 0, best_prim = -1, best_rank = 0x7fffffff;
+  int pend = 0;  // deferred leaf pass: the hit leaf child this lane carries, 0: none (leaf_vote)
   float best = 0.0f, bhi = 0.0f, second = 0.0f, qa = 0.0f, rcpa = 0.0f;
   bool overflow = false;
   unsigned nnode = 0, nprim = 0, nfall = 0;
@@ -2553,17 +2700,40 @@ void render_step_kernel(const RenderParams P) {
       // 1 / 2 / 3 / 4 steps: C2 14 538 / 14 713 / 14 829 / 14 843, C4 11 180 / 11 247 (before the
       // triangle dedupe) and 14 095 / 14 051 / 13 990 after it); the opt-in world-tree variants keep
       // one (more spills with two)
+      // (with the deferred leaf pass, C2 at 2 / 4 / 6 / 8 steps: 16.10 / 15.82 / 15.87 / 15.99 ms)
       constexpr int kUnroll = (F & F_WORLD) != 0 ? 1 : ((F & F_TRI) != 0 ? 2 : 4);
+      if constexpr (leaf_pass_min(F) > 0) {
+        // deferred leaf pass (leaf_vote): a lane whose search ends holding a leaf waits like any
+        // other, and a flush pass before the shading phase tests every leaf still held, so no lane
+        // settles with a leaf untested and `pend` is not live across the phase
 #pragma unroll
-      for (int u = 0; u < kUnroll; ++u)
-      if (mode == 1) {
-        RT_STEP_COUNT(0);
-        if (!trav_step<F>(S, tbase, ray, oi, finv, qa, rcpa, tmin, tmax, cur, sp, best, bhi, second, best_prim,
-                          best_rank, overflow, nnode, nprim))
-          mode = 2;
+        for (int u = 0; u < kUnroll; ++u) {
+          int n0 = 0, n1 = 0;
+          if (mode == 1) {
+            RT_STEP_COUNT(0);
+            if (!trav_node<F>(S, tbase, oi, finv, tmin, tmax, bhi, cur, sp, overflow, nnode, n0, n1)) mode = 2;
+          }
+          leaf_vote<F>(S, false, pend, n0, n1, ray, qa, rcpa, tmin, tmax, best, bhi, second, best_prim, best_rank,
+                       nprim);
+        }
+        // (the threshold as a kernel argument measured 1.5 % faster than the compile-time constant)
+        if (__ballot(mode == 1) == 0 || __popcll(__ballot(mode == 2)) >= P.shade_min) {
+          leaf_vote<F>(S, true, pend, 0, 0, ray, qa, rcpa, tmin, tmax, best, bhi, second, best_prim, best_rank,
+                       nprim);
+          break;
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u)
+        if (mode == 1) {
+          RT_STEP_COUNT(0);
+          if (!trav_step<F>(S, tbase, ray, oi, finv, qa, rcpa, tmin, tmax, cur, sp, best, bhi, second, best_prim,
+                            best_rank, overflow, nnode, nprim))
+            mode = 2;
+        }
+        // (the threshold as a kernel argument measured 1.5 % faster than the compile-time constant)
+        if (__ballot(mode == 1) == 0 || __popcll(__ballot(mode == 2)) >= P.shade_min) break;
       }
-      // (the threshold as a kernel argument measured 1.5 % faster than the compile-time constant)
-      if (__ballot(mode == 1) == 0 || __popcll(__ballot(mode == 2)) >= P.shade_min) break;
     }
   }
 
