@@ -17,7 +17,7 @@ MULTI_LIB = os.path.join(PKG, "librt_multi.so")
 EXAMPLES = os.path.join(ROOT, "examples")
 RT_MAIN = os.path.join(EXAMPLES, "bin", "rt_main")
 
-HIP_SOURCES = ["rt_kernels.hip", "rt_scene.cpp", "rt_obj.cpp", "rt_image.cpp", "rt_accum_blob.cpp",
+HIP_SOURCES = ["rt_kernels.hip", "rt_progressive.hip", "rt_scene.cpp", "rt_obj.cpp", "rt_image.cpp", "rt_accum_blob.cpp",
                "rt_noise_blob.cpp", "rt_validate.cpp"]
 # every header of csrc/ (rt_diag.h included): an edit to any of them rebuilds the library and changes
 # kernel_build_id() (tests/test_build_cpu.py checks that each local #include is covered)

@@ -1,4 +1,4 @@
-// rt_accum_blob.h — internal: what rt_kernels.hip shares with the host-only checkpoint code of
+// rt_accum_blob.h — internal: what rt_kernels.hip and rt_progressive.hip share with the host-only checkpoint code of
 // rt_accum_blob.cpp (the rt_accum_blob_* entry points themselves are declared in include/rt_hip.h).
 #ifndef RT_ACCUM_BLOB_H
 #define RT_ACCUM_BLOB_H

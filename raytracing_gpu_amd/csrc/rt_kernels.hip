@@ -1,5 +1,6 @@
 // rt_kernels.hip — gfx950 render path: RNG init, the persistent path-tracing megakernel and the
-// frame-buffer resolve, plus the C ABI of include/rt_hip.h.
+// frame-buffer resolve, plus the C ABI of include/rt_hip.h up to rt_draw.  The accumulators
+// (rt_accum, rt_noise, rt_adapt) and rt_render_tiles are rt_progressive.hip, over rt_ctx_internal.h.
 //
 // Reference semantics (file:line in daRoyalCacti/Raytracing_GPU):
 //   render_init            render.h:84-92
@@ -35,12 +36,15 @@
 #include <vector>
 
 #include "../../include/rt_hip.h"
-#include "rt_tile_list.h"
 #include "rt_accum_blob.h"
+#include "rt_ctx_internal.h"
 #include "rt_detmath.h"
 #include "rt_diag.h"
 #include "rt_host_geom.h"
+#include "rt_quant.h"
 #include "rt_xorwow.h"
+
+using namespace rtctx;  // fail, validate_args, device_ptr, render_dev: defined here, shared with rt_progressive.hip
 
 #define RT_PRIM_TYPE_MASK 0xff
 #define RT_PRIM_FLAG_UV 0x100      // material needs sphere u,v (image texture)
@@ -1954,7 +1958,6 @@ struct RenderParams {
   const uint32_t* tile_mask;
 };
 
-constexpr int kBlock = 256;
 constexpr int kAuditCap = 4096;
 constexpr int kTileShift = 3;  // camera-ray candidate lists per 8x8-pixel tile
 constexpr int kTileCap = 32;   // entries per tile list (a fuller tile traverses the tree)
@@ -2830,14 +2833,6 @@ __global__ __launch_bounds__(kInitBlock) void init_states_kernel(uint4* states, 
   }
 }
 
-// write_frame_buffer quantisation (color.h:40-44); NaN defined as 0.
-__device__ __forceinline__ int quant(float x) {
-  const float r = __builtin_sqrtf(x);
-  if (!(r == r)) return 0;
-  const float c = r < 0.0f ? 0.0f : (r > 0.999f ? 0.999f : r);
-  return (int)(256.0f * c);
-}
-
 // average_images (color.h:57-170) over fbs 0..nfb-1 in order, per owned pixel.
 __global__ __launch_bounds__(kBlock) void resolve_kernel(const float* __restrict__ fb, uint8_t* __restrict__ out,
                                                         long long per_fb, int nfb) {
@@ -2849,313 +2844,6 @@ __global__ __launch_bounds__(kBlock) void resolve_kernel(const float* __restrict
     acc += (float)(c * c) / (255.0f * 255.0f);
   }
   out[k] = (uint8_t)quant(acc / (float)nfb);
-}
-
-// Progressive accumulator (rt_accum): resolve_kernel's sum kept in memory between launches, so that
-// it can be cut after any frame buffer.  Element k: a = sums[k]; a += float(c*c) / (255*255) for
-// c = quant(fb[f][k]), f = 0..nfb-1 in order; sums[k] = a -- the same float operations in the same
-// order as resolve_kernel's acc (the sums start at 0.0f as acc does).
-// A pure stream: a lane owns 4 consecutive elements.  VEC (per_fb % 4 == 0, fb and sums 16-byte
-// aligned, so every frame buffer's start f*per_fb is too): one 16-byte load per frame buffer, one
-// 16-byte load and store of the sums, consecutive lanes on consecutive 16 bytes; elements past the
-// last whole group of 4, and everything when !VEC (odd per_fb, an offset fb pointer), go one by one.
-template <bool VEC>
-__global__ __launch_bounds__(kBlock) void accum_add_kernel(const float* __restrict__ fb, float* __restrict__ sums,
-                                                          long long per_fb, int nfb) {
-  const long long k0 = 4 * ((long long)blockIdx.x * kBlock + threadIdx.x);
-  if (k0 >= per_fb) return;
-  if (VEC && k0 + 4 <= per_fb) {
-    float4 a = *reinterpret_cast<const float4*>(sums + k0);
-#pragma unroll 4
-    for (int f = 0; f < nfb; ++f) {
-      const float4 v = *reinterpret_cast<const float4*>(fb + (long long)f * per_fb + k0);
-      const int cx = quant(v.x), cy = quant(v.y), cz = quant(v.z), cw = quant(v.w);
-      a.x += (float)(cx * cx) / (255.0f * 255.0f);
-      a.y += (float)(cy * cy) / (255.0f * 255.0f);
-      a.z += (float)(cz * cz) / (255.0f * 255.0f);
-      a.w += (float)(cw * cw) / (255.0f * 255.0f);
-    }
-    *reinterpret_cast<float4*>(sums + k0) = a;
-    return;
-  }
-  const long long k1 = k0 + 4 < per_fb ? k0 + 4 : per_fb;
-  for (long long k = k0; k < k1; ++k) {
-    float a = sums[k];
-    for (int f = 0; f < nfb; ++f) {
-      const int c = quant(fb[(long long)f * per_fb + k]);
-      a += (float)(c * c) / (255.0f * 255.0f);
-    }
-    sums[k] = a;
-  }
-}
-
-// accum_add_kernel with a noise monitor attached (rt_noise, include/rt_hip.h): the same single pass
-// over the frame buffers, the float sums updated by the same float operations in the same order
-// (byte-identical sums), and per value the integer moments S1 += c^2 (u32), S2 += c^4 (u64).  A fold
-// is refused before launch when the monitor would pass 32768 frame buffers, so S1 <= 2^15 x 65025
-// < 2^31 and S2 <= 2^15 x 65025^2 < 2^47 never wrap.  Same layout: a lane owns 4 consecutive values;
-// VEC (per_fb % 4 == 0; fb, sums, s1, s2 16-byte aligned): one 16-byte load and store for the S1
-// quad, two 16-byte pairs for S2.  Traffic per value: 4 nfb bytes in, 8 + 8 + 16 bytes of state.
-template <bool VEC>
-__global__ __launch_bounds__(kBlock) void accum_add_stats_kernel(const float* __restrict__ fb, float* __restrict__ sums,
-                                                                uint32_t* __restrict__ s1, unsigned long long* __restrict__ s2,
-                                                                long long per_fb, int nfb) {
-  const long long k0 = 4 * ((long long)blockIdx.x * kBlock + threadIdx.x);
-  if (k0 >= per_fb) return;
-  if (VEC && k0 + 4 <= per_fb) {
-    float4 a = *reinterpret_cast<const float4*>(sums + k0);
-    uint4 m1 = *reinterpret_cast<const uint4*>(s1 + k0);
-    ulonglong2 m2a = *reinterpret_cast<const ulonglong2*>(s2 + k0);
-    ulonglong2 m2b = *reinterpret_cast<const ulonglong2*>(s2 + k0 + 2);
-#pragma unroll 4
-    for (int f = 0; f < nfb; ++f) {
-      const float4 v = *reinterpret_cast<const float4*>(fb + (long long)f * per_fb + k0);
-      const int cx = quant(v.x), cy = quant(v.y), cz = quant(v.z), cw = quant(v.w);
-      a.x += (float)(cx * cx) / (255.0f * 255.0f);
-      a.y += (float)(cy * cy) / (255.0f * 255.0f);
-      a.z += (float)(cz * cz) / (255.0f * 255.0f);
-      a.w += (float)(cw * cw) / (255.0f * 255.0f);
-      const uint32_t qx = (uint32_t)(cx * cx), qy = (uint32_t)(cy * cy), qz = (uint32_t)(cz * cz), qw = (uint32_t)(cw * cw);
-      m1.x += qx;
-      m1.y += qy;
-      m1.z += qz;
-      m1.w += qw;
-      m2a.x += (unsigned long long)qx * qx;
-      m2a.y += (unsigned long long)qy * qy;
-      m2b.x += (unsigned long long)qz * qz;
-      m2b.y += (unsigned long long)qw * qw;
-    }
-    *reinterpret_cast<float4*>(sums + k0) = a;
-    *reinterpret_cast<uint4*>(s1 + k0) = m1;
-    *reinterpret_cast<ulonglong2*>(s2 + k0) = m2a;
-    *reinterpret_cast<ulonglong2*>(s2 + k0 + 2) = m2b;
-    return;
-  }
-  const long long k1 = k0 + 4 < per_fb ? k0 + 4 : per_fb;
-  for (long long k = k0; k < k1; ++k) {
-    float a = sums[k];
-    uint32_t m1 = s1[k];
-    unsigned long long m2 = s2[k];
-    for (int f = 0; f < nfb; ++f) {
-      const int c = quant(fb[(long long)f * per_fb + k]);
-      a += (float)(c * c) / (255.0f * 255.0f);
-      const uint32_t q = (uint32_t)(c * c);
-      m1 += q;
-      m2 += (unsigned long long)q * q;
-    }
-    sums[k] = a;
-    s1[k] = m1;
-    s2[k] = m2;
-  }
-}
-
-// The noise of the n frame buffers a monitor has seen (definitions in include/rt_hip.h).  One
-// 256-lane workgroup per tile of 16 x 16 pixels over (owned-row index, column), one lane per pixel;
-// a wave holds 4 tile rows of 16 pixels.  Per pixel, over its channels j, in unsigned 64-bit
-// integers (n <= 32768: n S2 and S1^2 <= 4.6e18 each, the three-channel sum <= 1.4e19 < 2^64; every
-// term n S2 - S1^2 >= 0 by Cauchy-Schwarz):  D = sum_j (n S2_j - S1_j^2),  S = sum_j S1_j;  then in
-// double, in this order:  a = D / (3.0 n n (n - 1) 4228250625.0),  m = max(S / (3.0 n 65025.0), 2^-16),
-// noise = float(128.0 sqrt(a / m)) >= 0.  Lanes outside a partial tile hold noise 0 and are not
-// counted.  Outputs: map[row][col] (may be null); per tile the maximum (shuffles within the wave, LDS
-// across the four) and the count of pixels with noise > threshold (ballot + popcount).  The image-wide
-// maximum and count come from the tile arrays in noise_reduce_kernel (one atomic per tile on one
-// address serialises: 32 400 tiles at 3840 x 2159 took longer than reading the moments).  No float is
-// summed anywhere: every output is independent of the order of reduction.
-// (the per-pixel formula and the tile reduction are functions of their own: the adaptive accumulator's
-// adapt_measure_kernel runs the same device code with a per-tile n)
-__device__ __forceinline__ float pixel_noise(const uint32_t* __restrict__ s1, const unsigned long long* __restrict__ s2,
-                                             long long px, int n) {
-  unsigned long long D = 0, S = 0;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const unsigned long long m1 = s1[3 * px + j], m2 = s2[3 * px + j];
-    D += (unsigned long long)n * m2 - m1 * m1;
-    S += m1;
-  }
-  const double dn = (double)n, dn1 = (double)(n - 1);
-  const double a = (double)D / (3.0 * dn * dn * dn1 * 4228250625.0);
-  double m = (double)S / (3.0 * dn * 65025.0);
-  if (m < 0x1p-16) m = 0x1p-16;
-  return (float)(128.0 * __builtin_sqrt(a / m));
-}
-// A 256-lane workgroup's maximum of noise and count of lanes with noise > threshold, into tile_max[tile]
-// and tile_above[tile] (wave_max, wave_above: 4 LDS words each).
-__device__ __forceinline__ void noise_tile_reduce(bool valid, float noise, float threshold, float* wave_max, int* wave_above,
-                                                  int tile, float* __restrict__ tile_max, int32_t* __restrict__ tile_above) {
-  const int lane = threadIdx.x;
-  const unsigned long long hot = __ballot(valid && noise > threshold);
-  float mx = noise;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-  const int wave = lane >> 6;
-  if ((lane & 63) == 0) {
-    wave_max[wave] = mx;
-    wave_above[wave] = __popcll(hot);
-  }
-  __syncthreads();
-  if (lane == 0) {
-    const float t = fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]));
-    const int cnt = wave_above[0] + wave_above[1] + wave_above[2] + wave_above[3];
-    tile_max[tile] = t;
-    tile_above[tile] = cnt;
-  }
-}
-__global__ __launch_bounds__(256) void noise_measure_kernel(const uint32_t* __restrict__ s1,
-                                                            const unsigned long long* __restrict__ s2, int n, int rows,
-                                                            int width, float threshold, float* __restrict__ map,
-                                                            float* __restrict__ tile_max, int32_t* __restrict__ tile_above) {
-  __shared__ float wave_max[4];
-  __shared__ int wave_above[4];
-  const int lane = threadIdx.x;
-  const int col = blockIdx.x * 16 + (lane & 15), row = blockIdx.y * 16 + (lane >> 4);
-  const bool valid = col < width && row < rows;
-  float noise = 0.0f;
-  if (valid) {
-    const long long px = (long long)row * width + col;
-    noise = pixel_noise(s1, s2, px, n);
-    if (map) map[px] = noise;
-  }
-  noise_tile_reduce(valid, noise, threshold, wave_max, wave_above, blockIdx.y * gridDim.x + blockIdx.x, tile_max,
-                    tile_above);
-}
-
-// Image-wide maximum (as the bit pattern of the non-negative float, in the low word of totals[1]) and
-// count (totals[0]) from noise_measure_kernel's tile arrays: one 256-lane workgroup strides over the
-// tiles; a maximum and an integer sum, so the order does not matter.
-__global__ __launch_bounds__(256) void noise_reduce_kernel(const float* __restrict__ tile_max,
-                                                           const int32_t* __restrict__ tile_above, int tiles,
-                                                           unsigned long long* __restrict__ totals) {
-  __shared__ float wave_max[4];
-  __shared__ unsigned long long wave_above[4];
-  const int lane = threadIdx.x;
-  float mx = 0.0f;
-  unsigned long long cnt = 0;
-  for (int t = lane; t < tiles; t += 256) {
-    mx = fmaxf(mx, tile_max[t]);
-    cnt += (unsigned long long)tile_above[t];
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    mx = fmaxf(mx, __shfl_xor(mx, d));
-    cnt += __shfl_xor(cnt, d);
-  }
-  if ((lane & 63) == 0) {
-    wave_max[lane >> 6] = mx;
-    wave_above[lane >> 6] = cnt;
-  }
-  __syncthreads();
-  if (lane == 0) {
-    totals[0] = wave_above[0] + wave_above[1] + wave_above[2] + wave_above[3];
-    totals[1] = __float_as_uint(fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3])));
-  }
-}
-
-// The image of the nfb frame buffers folded into sums: resolve_kernel's last line.  VEC (sums 16-byte,
-// out 4-byte aligned): 4 sums in, 4 bytes out per lane.
-template <bool VEC>
-__global__ __launch_bounds__(kBlock) void accum_image_kernel(const float* __restrict__ sums, uint8_t* __restrict__ out,
-                                                            long long n, int nfb) {
-  const long long k0 = 4 * ((long long)blockIdx.x * kBlock + threadIdx.x);
-  if (k0 >= n) return;
-  const float d = (float)nfb;
-  if (VEC && k0 + 4 <= n) {
-    const float4 a = *reinterpret_cast<const float4*>(sums + k0);
-    const uint32_t q = (uint32_t)quant(a.x / d) | (uint32_t)quant(a.y / d) << 8 | (uint32_t)quant(a.z / d) << 16 |
-                       (uint32_t)quant(a.w / d) << 24;
-    *reinterpret_cast<uint32_t*>(out + k0) = q;
-    return;
-  }
-  const long long k1 = k0 + 4 < n ? k0 + 4 : n;
-  for (long long k = k0; k < k1; ++k) out[k] = (uint8_t)quant(sums[k] / d);
-}
-
-// ---- launches over a set of noise tiles (rt_render_tiles) and the adaptive accumulator (rt_adapt)
-// "Noise tile" here is always the noise monitor's tile of 16 x 16 pixels over (owned-row index, column)
-// (rtacc::kNoiseTile), never the 8 x 8 camera-ray tile of kTileShift.
-//
-// The item list of a launch over the listed noise tiles: RenderParams::perm for the render kernels, which
-// decode item = q * fb_count * W + f * W + i (row position q, frame buffer f, column i).  One 256-lane
-// workgroup per listed tile, one lane per pixel; ntile[k] = {tile id, base, row stride, fb stride}: pixel
-// (ly, lx) of the tile in frame buffer f goes to position base + ly * row stride + f * fb stride + lx.  The
-// host (tile_list_build) chooses the strides: tile-major (a tile's pixels of one fb in adjacent claims) or
-// row-major (ascending items), and guarantees that the positions are a permutation of 0 .. n_items - 1.
-__global__ __launch_bounds__(256) void tile_items_kernel(const uint4* __restrict__ ntile, int tiles_x, int rows, int width,
-                                                         int fb_count, uint32_t* __restrict__ perm) {
-  const uint4 d = ntile[blockIdx.x];
-  const int lane = threadIdx.x, lx = lane & 15, ly = lane >> 4;
-  const int col = (int)(d.x % (unsigned)tiles_x) * 16 + lx, row = (int)(d.x / (unsigned)tiles_x) * 16 + ly;
-  if (col >= width || row >= rows) return;
-  const unsigned long long first = (unsigned long long)row * fb_count * width + col;
-  const unsigned long long pos = (unsigned long long)d.y + (unsigned long long)ly * d.z + lx;
-  for (int f = 0; f < fb_count; ++f) perm[pos + (unsigned long long)f * d.w] = (uint32_t)(first + (unsigned long long)f * width);
-}
-
-// rt_adapt: the nfb frame buffers at fb folded into the listed (active) noise tiles' values: the float sum
-// by accum_add_kernel's operations in its order, S1 and S2 as accum_add_stats_kernel keeps them.  One
-// workgroup per listed tile: the traffic is the active tiles', not the image's.  A tile row is 16 pixels =
-// 48 consecutive values; the 256 lanes take the tile's 768 values in three passes, consecutive lanes on
-// consecutive values of a row (one lane per pixel, three values 12 bytes apart, measured 127.7 us at
-// 1200 x 800 x 10 fb against this layout's 48.6 us).
-__global__ __launch_bounds__(256) void adapt_fold_kernel(const uint4* __restrict__ ntile, int tiles_x, int rows, int width,
-                                                         const float* __restrict__ fb, long long per_fb, int nfb,
-                                                         float* __restrict__ sums, uint32_t* __restrict__ s1,
-                                                         unsigned long long* __restrict__ s2) {
-  const unsigned id = ntile[blockIdx.x].x;
-  const int row0 = (int)(id / (unsigned)tiles_x) * 16, v0 = (int)(id % (unsigned)tiles_x) * 48;  // first row, first value of a row
-#pragma unroll
-  for (int pass = 0; pass < 3; ++pass) {
-    const int v = pass * 256 + (int)threadIdx.x;
-    const int row = row0 + v / 48, vx = v0 + v % 48;
-    if (row >= rows || vx >= 3 * width) continue;
-    const long long k = (long long)row * width * 3 + vx;
-    float a = sums[k];
-    uint32_t m1 = s1[k];
-    unsigned long long m2 = s2[k];
-    for (int f = 0; f < nfb; ++f) {
-      const int c = quant(fb[(long long)f * per_fb + k]);
-      a += (float)(c * c) / (255.0f * 255.0f);
-      const uint32_t q = (uint32_t)(c * c);
-      m1 += q;
-      m2 += (unsigned long long)q * q;
-    }
-    sums[k] = a;
-    s1[k] = m1;
-    s2[k] = m2;
-  }
-}
-
-// rt_adapt: noise_measure_kernel over listed noise tiles (list null: over every tile, tile = blockIdx.x),
-// each with its own n = tile_n[tile] >= 2; same per-pixel code, same tile reduction.
-__global__ __launch_bounds__(256) void adapt_measure_kernel(const uint4* __restrict__ ntile, const int32_t* __restrict__ tile_n,
-                                                            const uint32_t* __restrict__ s1,
-                                                            const unsigned long long* __restrict__ s2, int tiles_x, int rows,
-                                                            int width, float threshold, float* __restrict__ map,
-                                                            float* __restrict__ tile_max, int32_t* __restrict__ tile_above) {
-  __shared__ float wave_max[4];
-  __shared__ int wave_above[4];
-  const int tile = ntile ? (int)ntile[blockIdx.x].x : (int)blockIdx.x;
-  const int lane = threadIdx.x;
-  const int col = (tile % tiles_x) * 16 + (lane & 15), row = (tile / tiles_x) * 16 + (lane >> 4);
-  const bool valid = col < width && row < rows;
-  float noise = 0.0f;
-  if (valid) {
-    const long long px = (long long)row * width + col;
-    noise = pixel_noise(s1, s2, px, tile_n[tile]);
-    if (map) map[px] = noise;
-  }
-  noise_tile_reduce(valid, noise, threshold, wave_max, wave_above, tile, tile_max, tile_above);
-}
-
-// rt_adapt: accum_image_kernel with the divisor of the pixel's noise tile, out = quant(sum / n_t); one lane
-// per pixel.
-__global__ __launch_bounds__(kBlock) void adapt_image_kernel(const float* __restrict__ sums, const int32_t* __restrict__ tile_n,
-                                                            int tiles_x, int rows, int width, uint8_t* __restrict__ out) {
-  const long long px = (long long)blockIdx.x * kBlock + threadIdx.x;
-  if (px >= (long long)rows * width) return;
-  const int row = (int)(px / width), col = (int)(px - (long long)row * width);
-  const float d = (float)tile_n[(row >> 4) * tiles_x + (col >> 4)];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) out[3 * px + j] = (uint8_t)quant(sums[3 * px + j] / d);
 }
 
 // Split items (render_step_kernel split_mode 2): the fb value of each of the first n_split items
@@ -3640,15 +3328,6 @@ int scene_features(const rt_scene_soa* s) {
   return f;
 }
 
-int fail(rt_ctx* c, int code, const std::string& msg) {
-  if (c) c->err = msg;
-  return code;
-}
-#define HIPCHK(ctx, call)                                                                          \
-  do {                                                                                             \
-    hipError_t e_ = (call);                                                                        \
-    if (e_ != hipSuccess) return fail(ctx, RT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 template <class T>
 int upload(rt_ctx* c, const T* src, size_t n, const T** dst) {
@@ -4155,7 +3834,16 @@ int probe_schedule(rt_ctx* c, long long items, int spp, int width, int fbc, int 
   return RT_OK;
 }
 
-int validate_args(rt_ctx* c, const rt_render_args* a) {
+}  // namespace
+
+// ---- what rt_progressive.hip shares with this file (rt_ctx_internal.h), render_dev further down
+int rtctx::fail(rt_ctx* c, int code, const std::string& msg) {
+  if (c) c->err = msg;
+  return code;
+}
+rtctx::View rtctx::view(const rt_ctx* c) { return {c->device, c->stream, c->have_scene, c->scene_gen, c->scene_fp}; }
+
+int rtctx::validate_args(rt_ctx* c, const rt_render_args* a) {
   if (!a) return fail(c, RT_ERR_ARG, "null args");
   if (a->width <= 0 || a->height <= 0 || a->spp <= 0 || a->fb_count <= 0 || a->fb_first < 0 || a->max_depth <= 0)
     return fail(c, RT_ERR_ARG, "bad render args");
@@ -4165,7 +3853,23 @@ int validate_args(rt_ctx* c, const rt_render_args* a) {
   return RT_OK;
 }
 
-}  // namespace
+bool rtctx::states_are(const rt_ctx* c, int width, int height, uint64_t seed) {
+  return c->states && c->states_n == (long long)width * height && c->states_seed == seed;
+}
+int rtctx::ensure_states(rt_ctx* c, int width, int height, uint64_t seed) {
+  return states_are(c, width, height, seed) ? RT_OK : rt_render_init(c, width, height, seed);
+}
+
+// A pointer the GPU kernels may write directly: device (or managed) memory.  Host memory, pinned
+// or pageable, is staged through a temporary device buffer by rt_render / rt_resolve.
+bool rtctx::device_ptr(const void* p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged || at.isManaged;
+}
 
 extern "C" {
 
@@ -4845,25 +4549,6 @@ int rt_render_init(rt_ctx* c, int32_t width, int32_t height, uint64_t seed) {
   return RT_OK;
 }
 
-namespace {
-// A pointer the GPU kernels may write directly: device (or managed) memory.  Host memory, pinned
-// or pageable, is staged through a temporary device buffer by rt_render / rt_resolve.
-bool device_ptr(const void* p) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged || at.isManaged;
-}
-// A launch over a caller-built item list (rt_render_tiles): perm[0 .. n_items) are the items to render.
-struct TileLaunch {
-  const uint32_t* perm;
-  unsigned long long n_items;
-};
-int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* counters, const TileLaunch* tl = nullptr);
-}  // namespace
-
 int rt_render(rt_ctx* c, const rt_render_args* a, float* fb, rt_counters* counters) {
   if (!c) return RT_ERR_ARG;
   int rc = validate_args(c, a);
@@ -4882,12 +4567,13 @@ int rt_render(rt_ctx* c, const rt_render_args* a, float* fb, rt_counters* counte
   return rc;
 }
 
-namespace {
+}  // extern "C"
+
 // tl (a tile launch): the launch claims tl's items in tl's order and is isolated from the context's
 // schedule state -- no schedule is read, built or recorded (perm_key, pending_key, the split state and
 // host_cost / cost_key stay as they are; the schedule flags have no effect), no probe, no split samples,
 // n_long = 0, no item or row costs, rows in ascending order (the row-map cache is kept up to date).
-int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* counters, const TileLaunch* tl) {
+int rtctx::render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* counters, const TileLaunch* tl) {
   int rc = RT_OK;
   if (!c->have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
   if (!c->states || c->states_n != (long long)a->width * a->height || c->states_seed != a->seed)
@@ -5372,7 +5058,8 @@ int render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* c
     return fail(c, RT_ERR_HIP, "render kernel did not complete every sample");
   return RT_OK;
 }
-}  // namespace
+
+extern "C" {
 
 float rt_last_render_ms(const rt_ctx* c) { return c ? c->last_ms : 0.0f; }
 float rt_last_kernel_ms(const rt_ctx* c) { return c ? c->last_kernel_ms : 0.0f; }
@@ -5470,928 +5157,3 @@ int rt_draw(rt_ctx* c, const rt_render_args* a, uint8_t* png_rgb_host, rt_counte
 
 }  // extern "C"
 
-// ---------------------------------------------------------------------- progressive accumulator
-// draw() cut after any frame buffer: the float sums of average_images (color.h:57-170) stay on the
-// device between calls, the frame buffers of one chunk at a time go through `scratch`.
-struct rt_accum {
-  rt_ctx* ctx = nullptr;
-  rt_render_args args{};  // fb_count = frame buffers folded in
-  int32_t chunk = 1;
-  long long per_fb = 0;   // owned_rows x width x 3
-  long long scene_gen = 0;
-  uint64_t scene_fp = 0;
-  float* sums = nullptr;     // [per_fb]
-  float* scratch = nullptr;  // [chunk][per_fb], allocated by the first rt_accum_add
-  uint8_t* img = nullptr;    // [per_fb], allocated by the first rt_accum_image into host memory
-  // around the last accumulate launch (ev[0], ev[1]) and the last image launch (ev[2], ev[3])
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool add_timed = false, image_timed = false;
-  rt_noise* noise = nullptr;  // the attached monitor (not owned: rt_noise_destroy frees it)
-};
-
-// Noise monitor of an accumulator (include/rt_hip.h): the integer moments of c^2 per accumulator value.
-struct rt_noise {
-  rt_accum* acc = nullptr;  // null once the accumulator is destroyed (detached: calls are RT_ERR_STATE)
-  int device = 0;
-  long long per_fb = 0;     // the accumulator's
-  int rows = 0, width = 0, tiles_x = 0, tiles_y = 0;
-  int32_t fbs = 0;          // frame buffers folded in, at most rtacc::kNoiseMaxFbs
-  uint32_t* s1 = nullptr;            // [per_fb] sum of c^2
-  unsigned long long* s2 = nullptr;  // [per_fb] sum of c^4
-  // measure outputs: [tiles] maxima, [tiles] counts, then the image-wide count (u64) and maximum (u32 bits)
-  float* tile_max = nullptr;
-  int32_t* tile_above = nullptr;
-  unsigned long long* totals = nullptr;  // totals[0] = pixels above, low word of totals[1] = max bits
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool timed = false;
-};
-
-extern "C" int rt_accum_destroy(rt_accum* acc);
-extern "C" int rt_noise_destroy(rt_noise* nm);
-
-namespace {
-
-bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-// sums += the count frame buffers at fb_dev, queued on the context's stream.
-int accum_fold(rt_accum* acc, const float* fb_dev, int count) {
-  rt_ctx* c = acc->ctx;
-  const long long per_fb = acc->per_fb;
-  const unsigned blocks = (unsigned)(((per_fb + 3) / 4 + kBlock - 1) / kBlock);
-  rt_noise* nm = acc->noise;
-  if (nm && count > rtacc::kNoiseMaxFbs - nm->fbs) return fail(c, RT_ERR_ARG, "noise monitor: more than 32768 frame buffers");
-  HIPCHK(c, hipEventRecord(acc->ev[0], c->stream));
-  const bool vec = per_fb % 4 == 0 && aligned_to(fb_dev, 16) && aligned_to(acc->sums, 16);
-  if (nm && vec && aligned_to(nm->s1, 16) && aligned_to(nm->s2, 16))
-    hipLaunchKernelGGL(accum_add_stats_kernel<true>, dim3(blocks), dim3(kBlock), 0, c->stream, fb_dev, acc->sums, nm->s1,
-                       nm->s2, per_fb, count);
-  else if (nm)
-    hipLaunchKernelGGL(accum_add_stats_kernel<false>, dim3(blocks), dim3(kBlock), 0, c->stream, fb_dev, acc->sums, nm->s1,
-                       nm->s2, per_fb, count);
-  else if (vec)
-    hipLaunchKernelGGL(accum_add_kernel<true>, dim3(blocks), dim3(kBlock), 0, c->stream, fb_dev, acc->sums, per_fb, count);
-  else
-    hipLaunchKernelGGL(accum_add_kernel<false>, dim3(blocks), dim3(kBlock), 0, c->stream, fb_dev, acc->sums, per_fb, count);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(acc->ev[1], c->stream));
-  acc->add_timed = true;
-  acc->args.fb_count += count;
-  if (nm) nm->fbs += count;
-  return RT_OK;
-}
-
-// A fold of count frame buffers that the attached monitor would refuse (checked before anything is
-// rendered or written).
-bool noise_full(const rt_accum* acc, int32_t count) {
-  return acc->noise && count > rtacc::kNoiseMaxFbs - acc->noise->fbs;
-}
-
-int accum_new(rt_ctx* c, const rt_render_args* a, int32_t chunk_fbs, rt_accum** out) {
-  if (!c) return RT_ERR_ARG;
-  if (!out) return fail(c, RT_ERR_ARG, "null accumulator pointer");
-  *out = nullptr;
-  if (!a) return fail(c, RT_ERR_ARG, "null args");
-  rt_render_args one = *a;
-  one.fb_count = 1;
-  const int rc = validate_args(c, &one);
-  if (rc) return rc;
-  if (chunk_fbs < 1) return fail(c, RT_ERR_ARG, "chunk_fbs < 1");
-  if (a->fb_first > INT32_MAX - chunk_fbs) return fail(c, RT_ERR_ARG, "fb range overflows");
-  const long long per_fb = (long long)rt_owned_rows(a, nullptr) * a->width * 3;
-  if (per_fb <= 0) return fail(c, RT_ERR_ARG, "no rows owned");
-  if (!c->have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
-  HIPCHK(c, hipSetDevice(c->device));
-  rt_accum* acc = new rt_accum;
-  acc->ctx = c;
-  acc->args = *a;
-  acc->args.fb_count = 0;
-  acc->chunk = chunk_fbs;
-  acc->per_fb = per_fb;
-  acc->scene_gen = c->scene_gen;
-  acc->scene_fp = c->scene_fp;
-  for (hipEvent_t& e : acc->ev)
-    if (hipEventCreate(&e) != hipSuccess) {
-      e = nullptr;
-      rt_accum_destroy(acc);
-      return fail(c, RT_ERR_HIP, "hipEventCreate");
-    }
-  if (hipMalloc((void**)&acc->sums, (size_t)per_fb * sizeof(float)) != hipSuccess) {
-    acc->sums = nullptr;
-    rt_accum_destroy(acc);
-    return fail(c, RT_ERR_NOMEM, "hipMalloc accumulator sums");
-  }
-  if (hipMemsetAsync(acc->sums, 0, (size_t)per_fb * sizeof(float), c->stream) != hipSuccess) {
-    rt_accum_destroy(acc);
-    return fail(c, RT_ERR_HIP, "clear accumulator sums");
-  }
-  *out = acc;
-  return RT_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int rt_accum_create(rt_ctx* c, const rt_render_args* a, int32_t chunk_fbs, rt_accum** out) {
-  return accum_new(c, a, chunk_fbs, out);
-}
-
-int rt_accum_destroy(rt_accum* acc) {
-  if (!acc) return RT_ERR_ARG;
-  (void)hipSetDevice(acc->ctx->device);
-  (void)hipStreamSynchronize(acc->ctx->stream);
-  if (acc->noise) acc->noise->acc = nullptr;  // detached: the monitor's calls fail from here on
-  if (acc->sums) (void)hipFree(acc->sums);
-  if (acc->scratch) (void)hipFree(acc->scratch);
-  if (acc->img) (void)hipFree(acc->img);
-  for (hipEvent_t e : acc->ev)
-    if (e) (void)hipEventDestroy(e);
-  delete acc;
-  return RT_OK;
-}
-
-int rt_accum_add(rt_accum* acc, int32_t count, rt_counters* counters) {
-  if (!acc) return RT_ERR_ARG;
-  rt_ctx* c = acc->ctx;
-  if (count < 1) return fail(c, RT_ERR_ARG, "count < 1");
-  if (count > INT32_MAX - acc->args.fb_first - acc->args.fb_count) return fail(c, RT_ERR_ARG, "fb range overflows");
-  if (noise_full(acc, count)) return fail(c, RT_ERR_ARG, "noise monitor: more than 32768 frame buffers");
-  if (acc->scene_gen != c->scene_gen) return fail(c, RT_ERR_STATE, "scene uploaded again since the accumulator was created");
-  HIPCHK(c, hipSetDevice(c->device));
-  const rt_render_args& a = acc->args;
-  // the RNG states of (W, H, seed), as rt_draw makes them (rendering leaves them as they are)
-  if (!c->states || c->states_n != (long long)a.width * a.height || c->states_seed != a.seed) {
-    const int rc = rt_render_init(c, a.width, a.height, a.seed);
-    if (rc) return rc;
-  }
-  if (!acc->scratch && hipMalloc((void**)&acc->scratch, (size_t)acc->chunk * acc->per_fb * sizeof(float)) != hipSuccess) {
-    acc->scratch = nullptr;
-    return fail(c, RT_ERR_NOMEM, "hipMalloc accumulator frame buffers");
-  }
-  rt_counters total = {};
-  for (int32_t left = count; left > 0;) {
-    const int32_t n = std::min(left, acc->chunk);
-    rt_render_args r = a;
-    r.fb_first = a.fb_first + a.fb_count;
-    r.fb_count = n;
-    rt_counters cnt = {};
-    int rc = rt_render(c, &r, acc->scratch, &cnt);
-    if (!rc) rc = accum_fold(acc, acc->scratch, n);  // ordered before the next chunk's render on the stream
-    if (rc) return rc;
-    total.segments += cnt.segments;
-    total.node_tests += cnt.node_tests;
-    total.prim_tests += cnt.prim_tests;
-    total.samples += cnt.samples;
-    total.fallbacks += cnt.fallbacks;
-    left -= n;
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (counters) *counters = total;
-  return RT_OK;
-}
-
-int rt_accum_add_fbs(rt_accum* acc, const float* fb, int32_t count) {
-  if (!acc) return RT_ERR_ARG;
-  rt_ctx* c = acc->ctx;
-  if (!fb) return fail(c, RT_ERR_ARG, "null fb");
-  if (count < 1) return fail(c, RT_ERR_ARG, "count < 1");
-  if (count > INT32_MAX - acc->args.fb_first - acc->args.fb_count) return fail(c, RT_ERR_ARG, "fb range overflows");
-  if (noise_full(acc, count)) return fail(c, RT_ERR_ARG, "noise monitor: more than 32768 frame buffers");
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc = RT_OK;
-  float* tmp = nullptr;  // a host frame buffer is staged through device memory, as rt_resolve does
-  if (!device_ptr(fb)) {
-    const size_t bytes = (size_t)count * acc->per_fb * sizeof(float);
-    if (hipMalloc((void**)&tmp, bytes) != hipSuccess) return fail(c, RT_ERR_NOMEM, "hipMalloc frame buffer staging");
-    if (hipMemcpy(tmp, fb, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, RT_ERR_HIP, "copy frame buffer to device");
-  }
-  if (!rc) rc = accum_fold(acc, tmp ? tmp : fb, count);
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(c, RT_ERR_HIP, "accumulate kernel");
-  if (tmp) (void)hipFree(tmp);
-  return rc;
-}
-
-int rt_accum_image(rt_accum* acc, uint8_t* out, int32_t png_order) {
-  if (!acc) return RT_ERR_ARG;
-  rt_ctx* c = acc->ctx;
-  if (!out) return fail(c, RT_ERR_ARG, "null image");
-  if (png_order != 0 && png_order != 1) return fail(c, RT_ERR_ARG, "bad png_order");
-  const rt_render_args& a = acc->args;
-  HIPCHK(c, hipSetDevice(c->device));
-  const bool out_dev = device_ptr(out);
-  if (png_order && acc->per_fb != (long long)a.width * a.height * 3)
-    return fail(c, RT_ERR_ARG, "png_order needs the whole-image tiling");
-  if (png_order && out_dev) return fail(c, RT_ERR_ARG, "png_order needs a host image");
-  if (a.fb_count < 1) return fail(c, RT_ERR_STATE, "no frame buffer accumulated yet");
-  if (!out_dev && !acc->img && hipMalloc((void**)&acc->img, (size_t)acc->per_fb) != hipSuccess) {
-    acc->img = nullptr;
-    return fail(c, RT_ERR_NOMEM, "hipMalloc accumulator image");
-  }
-  uint8_t* img = out_dev ? out : acc->img;
-  const unsigned blocks = (unsigned)(((acc->per_fb + 3) / 4 + kBlock - 1) / kBlock);
-  HIPCHK(c, hipEventRecord(acc->ev[2], c->stream));
-  if (aligned_to(acc->sums, 16) && aligned_to(img, 4))
-    hipLaunchKernelGGL(accum_image_kernel<true>, dim3(blocks), dim3(kBlock), 0, c->stream, acc->sums, img, acc->per_fb, a.fb_count);
-  else
-    hipLaunchKernelGGL(accum_image_kernel<false>, dim3(blocks), dim3(kBlock), 0, c->stream, acc->sums, img, acc->per_fb, a.fb_count);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(acc->ev[3], c->stream));
-  acc->image_timed = true;
-  if (out_dev) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RT_OK;
-  }
-  if (!png_order) {
-    HIPCHK(c, hipMemcpyAsync(out, img, (size_t)acc->per_fb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RT_OK;
-  }
-  std::vector<uint8_t> tmp((size_t)acc->per_fb);
-  HIPCHK(c, hipMemcpyAsync(tmp.data(), img, tmp.size(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const size_t row = (size_t)a.width * 3;
-  for (int j = 0; j < a.height; ++j) memcpy(out + (size_t)(a.height - 1 - j) * row, tmp.data() + j * row, row);
-  return RT_OK;
-}
-
-int rt_accum_get_info(const rt_accum* acc, rt_accum_info* info) {
-  if (!acc) return RT_ERR_ARG;
-  if (!info) return fail(acc->ctx, RT_ERR_ARG, "null info");
-  info->args = acc->args;
-  info->n_values = acc->per_fb;
-  info->scene_fp = acc->scene_fp;
-  return RT_OK;
-}
-
-float rt_accum_last_add_ms(const rt_accum* acc) {
-  float ms = 0.0f;
-  if (!acc || !acc->add_timed || hipEventElapsedTime(&ms, acc->ev[0], acc->ev[1]) != hipSuccess) return 0.0f;
-  return ms;
-}
-float rt_accum_last_image_ms(const rt_accum* acc) {
-  float ms = 0.0f;
-  if (!acc || !acc->image_timed || hipEventElapsedTime(&ms, acc->ev[2], acc->ev[3]) != hipSuccess) return 0.0f;
-  return ms;
-}
-
-int rt_accum_save(rt_accum* acc, void* blob, size_t cap, size_t* need) {
-  if (!acc) return RT_ERR_ARG;
-  rt_ctx* c = acc->ctx;
-  const size_t total = rtacc::kHeaderBytes + (size_t)acc->per_fb * sizeof(float);
-  if (need) *need = total;
-  if (!blob && cap == 0) return RT_OK;  // size query
-  if (!blob || cap < total) return fail(c, RT_ERR_ARG, "checkpoint buffer too small");
-  HIPCHK(c, hipSetDevice(c->device));
-  // the sums land in the blob's payload, then the header is packed around them
-  float* payload = reinterpret_cast<float*>(static_cast<unsigned char*>(blob) + rtacc::kHeaderBytes);
-  HIPCHK(c, hipMemcpyAsync(payload, acc->sums, (size_t)acc->per_fb * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rt_accum_info info;
-  rt_accum_get_info(acc, &info);
-  if (rt_accum_blob_pack(&info, payload, blob, cap, nullptr)) return fail(c, RT_ERR_ARG, "pack checkpoint");
-  return RT_OK;
-}
-
-int rt_accum_load(rt_ctx* c, const void* blob, size_t n, int32_t chunk_fbs, rt_accum** out) {
-  if (!c) return RT_ERR_ARG;
-  if (!out) return fail(c, RT_ERR_ARG, "null accumulator pointer");
-  *out = nullptr;
-  rt_accum_info info;
-  if (rt_accum_blob_info(blob, n, &info)) return fail(c, RT_ERR_ARG, "malformed checkpoint");
-  if (!c->have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
-  if (info.scene_fp != c->scene_fp) return fail(c, RT_ERR_STATE, "checkpoint belongs to another scene");
-  if (info.args.fb_first > INT32_MAX - info.args.fb_count) return fail(c, RT_ERR_ARG, "malformed checkpoint");
-  rt_accum* acc = nullptr;
-  int rc = accum_new(c, &info.args, chunk_fbs, &acc);
-  if (rc) return rc;
-  if (acc->per_fb != info.n_values) rc = fail(c, RT_ERR_ARG, "malformed checkpoint");
-  const unsigned char* payload = static_cast<const unsigned char*>(blob) + rtacc::kHeaderBytes;
-  if (!rc && (hipMemcpyAsync(acc->sums, payload, (size_t)acc->per_fb * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-              hipStreamSynchronize(c->stream) != hipSuccess))
-    rc = fail(c, RT_ERR_HIP, "copy checkpoint sums to device");
-  if (rc) {
-    rt_accum_destroy(acc);
-    return rc;
-  }
-  acc->args.fb_count = info.args.fb_count;
-  *out = acc;
-  return RT_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------- noise monitor
-namespace {
-
-// A monitor attached to acc with every moment 0 (queued on the context's stream).
-int noise_new(rt_accum* acc, rt_noise** out) {
-  rt_ctx* c = acc->ctx;
-  const long long rows = acc->per_fb / (3LL * acc->args.width);
-  const long long tiles_x = (acc->args.width + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
-  const long long tiles_y = (rows + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
-  if (tiles_y > 65535 || tiles_x * tiles_y > INT32_MAX) return fail(c, RT_ERR_ARG, "noise monitor: too many tiles");
-  HIPCHK(c, hipSetDevice(c->device));
-  rt_noise* nm = new rt_noise;
-  nm->device = c->device;
-  nm->per_fb = acc->per_fb;
-  nm->rows = (int)rows;
-  nm->width = acc->args.width;
-  nm->tiles_x = (int)tiles_x;
-  nm->tiles_y = (int)tiles_y;
-  const size_t nv = (size_t)acc->per_fb, tiles = (size_t)(tiles_x * tiles_y);
-  bool ok = hipMalloc((void**)&nm->s1, nv * sizeof(uint32_t)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&nm->s2, nv * sizeof(unsigned long long)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&nm->tile_max, tiles * sizeof(float)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&nm->tile_above, tiles * sizeof(int32_t)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&nm->totals, 2 * sizeof(unsigned long long)) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    rt_noise_destroy(nm);
-    return fail(c, RT_ERR_NOMEM, "hipMalloc noise monitor");
-  }
-  ok = hipEventCreate(&nm->ev[0]) == hipSuccess && hipEventCreate(&nm->ev[1]) == hipSuccess;
-  ok = ok && hipMemsetAsync(nm->s1, 0, nv * sizeof(uint32_t), c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(nm->s2, 0, nv * sizeof(unsigned long long), c->stream) == hipSuccess;
-  if (!ok) {
-    rt_noise_destroy(nm);
-    return fail(c, RT_ERR_HIP, "set up noise monitor");
-  }
-  nm->acc = acc;
-  acc->noise = nm;
-  *out = nm;
-  return RT_OK;
-}
-
-// noise_measure_kernel over the whole monitor, then the reduction of its tile arrays, queued on the
-// context's stream; map_dev may be null.
-int noise_run(rt_noise* nm, float threshold, float* map_dev) {
-  rt_ctx* c = nm->acc->ctx;
-  HIPCHK(c, hipEventRecord(nm->ev[0], c->stream));
-  hipLaunchKernelGGL(noise_measure_kernel, dim3(nm->tiles_x, nm->tiles_y), dim3(256), 0, c->stream, nm->s1, nm->s2, nm->fbs,
-                     nm->rows, nm->width, threshold, map_dev, nm->tile_max, nm->tile_above);
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(noise_reduce_kernel, dim3(1), dim3(256), 0, c->stream, nm->tile_max, nm->tile_above,
-                     nm->tiles_x * nm->tiles_y, nm->totals);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(nm->ev[1], c->stream));
-  nm->timed = true;
-  return RT_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int rt_noise_create(rt_accum* acc, rt_noise** out) {
-  if (!acc) return RT_ERR_ARG;
-  rt_ctx* c = acc->ctx;
-  if (!out) return fail(c, RT_ERR_ARG, "null monitor pointer");
-  *out = nullptr;
-  if (acc->noise) return fail(c, RT_ERR_STATE, "the accumulator has a noise monitor already");
-  if (acc->args.fb_count != 0) return fail(c, RT_ERR_STATE, "a noise monitor sees every frame buffer or none: the accumulator is not empty");
-  return noise_new(acc, out);
-}
-
-int rt_noise_destroy(rt_noise* nm) {
-  if (!nm) return RT_ERR_ARG;
-  (void)hipSetDevice(nm->device);
-  if (nm->acc) {
-    (void)hipStreamSynchronize(nm->acc->ctx->stream);
-    nm->acc->noise = nullptr;  // the accumulator goes on with accum_add_kernel
-  }
-  if (nm->s1) (void)hipFree(nm->s1);
-  if (nm->s2) (void)hipFree(nm->s2);
-  if (nm->tile_max) (void)hipFree(nm->tile_max);
-  if (nm->tile_above) (void)hipFree(nm->tile_above);
-  if (nm->totals) (void)hipFree(nm->totals);
-  for (hipEvent_t e : nm->ev)
-    if (e) (void)hipEventDestroy(e);
-  delete nm;
-  return RT_OK;
-}
-
-int rt_noise_measure(rt_noise* nm, float threshold, rt_noise_report* rep, float* tile_max, int32_t* tile_above) {
-  if (!nm) return RT_ERR_ARG;
-  if (!nm->acc) return RT_ERR_STATE;  // detached
-  rt_ctx* c = nm->acc->ctx;
-  if (nm->fbs < 2) return fail(c, RT_ERR_STATE, "noise needs at least 2 frame buffers");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int rc = noise_run(nm, threshold, nullptr);
-  if (rc) return rc;
-  const size_t tiles = (size_t)nm->tiles_x * nm->tiles_y;
-  unsigned long long totals[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(totals, nm->totals, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
-  if (tile_max) HIPCHK(c, hipMemcpyAsync(tile_max, nm->tile_max, tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (tile_above) HIPCHK(c, hipMemcpyAsync(tile_above, nm->tile_above, tiles * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (rep) {
-    rep->fbs = nm->fbs;
-    rep->tiles_x = nm->tiles_x;
-    rep->tiles_y = nm->tiles_y;
-    rep->pad = 0;
-    rep->pixels = (int64_t)nm->rows * nm->width;
-    rep->pixels_above = (int64_t)totals[0];
-    rep->threshold = threshold;
-    const uint32_t bits = (uint32_t)totals[1];
-    memcpy(&rep->max_noise, &bits, sizeof(bits));
-  }
-  return RT_OK;
-}
-
-int rt_noise_map(rt_noise* nm, float* out) {
-  if (!nm) return RT_ERR_ARG;
-  if (!nm->acc) return RT_ERR_STATE;  // detached
-  rt_ctx* c = nm->acc->ctx;
-  if (!out) return fail(c, RT_ERR_ARG, "null map");
-  if (nm->fbs < 2) return fail(c, RT_ERR_STATE, "noise needs at least 2 frame buffers");
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t bytes = (size_t)nm->rows * nm->width * sizeof(float);
-  float* tmp = nullptr;  // a host map is staged through device memory
-  if (!device_ptr(out) && hipMalloc((void**)&tmp, bytes) != hipSuccess) return fail(c, RT_ERR_NOMEM, "hipMalloc noise map");
-  int rc = noise_run(nm, 0.0f, tmp ? tmp : out);
-  if (!rc && tmp && hipMemcpyAsync(out, tmp, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-    rc = fail(c, RT_ERR_HIP, "copy noise map");
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(c, RT_ERR_HIP, "noise measure kernel");
-  if (tmp) (void)hipFree(tmp);
-  return rc;
-}
-
-float rt_noise_last_measure_ms(const rt_noise* nm) {
-  float ms = 0.0f;
-  if (!nm || !nm->timed || hipEventElapsedTime(&ms, nm->ev[0], nm->ev[1]) != hipSuccess) return 0.0f;
-  return ms;
-}
-
-int rt_noise_save(rt_noise* nm, void* blob, size_t cap, size_t* need) {
-  if (!nm) return RT_ERR_ARG;
-  if (!nm->acc) return RT_ERR_STATE;  // detached
-  rt_ctx* c = nm->acc->ctx;
-  const size_t nv = (size_t)nm->per_fb;
-  const size_t total = rtacc::kHeaderBytes + nv * (sizeof(unsigned long long) + sizeof(uint32_t));
-  if (need) *need = total;
-  if (!blob && cap == 0) return RT_OK;  // size query
-  if (!blob || cap < total) return fail(c, RT_ERR_ARG, "noise blob buffer too small");
-  HIPCHK(c, hipSetDevice(c->device));
-  // the moments land in the blob's payload, then the header is packed around them
-  unsigned char* p2 = static_cast<unsigned char*>(blob) + rtacc::kHeaderBytes;
-  unsigned char* p1 = p2 + nv * sizeof(unsigned long long);
-  HIPCHK(c, hipMemcpyAsync(p2, nm->s2, nv * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(p1, nm->s1, nv * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rt_accum_info info;
-  rt_accum_get_info(nm->acc, &info);
-  info.args.fb_count = nm->fbs;
-  if (rt_noise_blob_pack(&info, reinterpret_cast<const uint32_t*>(p1), reinterpret_cast<const uint64_t*>(p2), blob, cap, nullptr))
-    return fail(c, RT_ERR_ARG, "pack noise blob");
-  return RT_OK;
-}
-
-int rt_noise_load(rt_accum* acc, const void* blob, size_t n, rt_noise** out) {
-  if (!acc) return RT_ERR_ARG;
-  rt_ctx* c = acc->ctx;
-  if (!out) return fail(c, RT_ERR_ARG, "null monitor pointer");
-  *out = nullptr;
-  rt_accum_info info, have;
-  if (rt_noise_blob_info(blob, n, &info)) return fail(c, RT_ERR_ARG, "malformed noise blob");
-  if (acc->noise) return fail(c, RT_ERR_STATE, "the accumulator has a noise monitor already");
-  rt_accum_get_info(acc, &have);
-  const rt_render_args &a = info.args, &b = have.args;
-  if (a.width != b.width || a.height != b.height || a.spp != b.spp || a.fb_first != b.fb_first || a.fb_count != b.fb_count ||
-      a.max_depth != b.max_depth || a.cam_mode != b.cam_mode || a.band_rows != b.band_rows || a.band_first != b.band_first ||
-      a.band_stride != b.band_stride || a.stats != b.stats || a.flags != b.flags || a.seed != b.seed ||
-      info.n_values != have.n_values || info.scene_fp != have.scene_fp)
-    return fail(c, RT_ERR_STATE, "noise blob belongs to another accumulator state");
-  rt_noise* nm = nullptr;
-  int rc = noise_new(acc, &nm);
-  if (rc) return rc;
-  const size_t nv = (size_t)acc->per_fb;
-  const unsigned char* p2 = static_cast<const unsigned char*>(blob) + rtacc::kHeaderBytes;
-  const unsigned char* p1 = p2 + nv * sizeof(unsigned long long);
-  if (hipMemcpyAsync(nm->s2, p2, nv * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(nm->s1, p1, nv * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess) {
-    rt_noise_destroy(nm);
-    return fail(c, RT_ERR_HIP, "copy noise moments to device");
-  }
-  nm->fbs = info.args.fb_count;
-  *out = nm;
-  return RT_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------- tile launches, adaptive accumulator
-// rt_render over a set of the noise monitor's tiles (16 x 16 pixels over (owned-row index, column)), and
-// the accumulator that stops rendering a tile once its own noise estimate is low enough (include/rt_hip.h).
-struct rt_adapt {
-  rt_ctx* ctx = nullptr;
-  rt_render_args args{};  // fb_count = frame buffers rendered for the tiles still active (max n_t)
-  int32_t chunk = 1;
-  long long per_fb = 0;  // owned_rows x width x 3
-  int rows = 0, tiles_x = 0, tiles_y = 0;
-  long long scene_gen = 0;
-  float* sums = nullptr;             // [per_fb]
-  uint32_t* s1 = nullptr;            // [per_fb] sum of c^2
-  unsigned long long* s2 = nullptr;  // [per_fb] sum of c^4
-  float* scratch = nullptr;          // [chunk][per_fb], allocated by the first rt_adapt_add
-  uint32_t* perm = nullptr;          // [chunk x owned pixels] item list of a tile launch, with scratch
-  uint4* ntile = nullptr;            // [tiles] the active noise tiles' list (tile_items_kernel's records)
-  int32_t* tile_n = nullptr;         // [tiles] n_t
-  float* tile_max = nullptr;         // [tiles] measure outputs
-  int32_t* tile_above = nullptr;
-  uint8_t* img = nullptr;            // [per_fb], allocated by the first rt_adapt_image into host memory
-  std::vector<int32_t> n_t;          // host copy of tile_n (kept alive for its upload)
-  std::vector<int32_t> active;       // ids of the active tiles, ascending
-  std::vector<rttile::Rec> ntile_host;     // what ntile holds (kept alive for its upload)
-  std::vector<float> h_max;          // host copies of the measure outputs; once have_measure, the retired
-  std::vector<int32_t> h_above;      // tiles' entries are current at threshold `measured` (theirs never change)
-  float measured = 0.0f;
-  bool have_measure = false;
-  // around the last fold (ev[0], ev[1]) and the last retire's measure kernel (ev[2], ev[3])
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool add_timed = false, retire_timed = false;
-};
-
-namespace {
-static_assert(rttile::kTile == rtacc::kNoiseTile, "tile launches use the noise monitor's tiles");
-inline void ntile_size(int id, int tiles_x, int rows, int width, int& tw, int& th) { rttile::size(id, tiles_x, rows, width, tw, th); }
-
-// The records uploaded to ntile_dev and expanded into perm_dev (both large enough), queued on the stream;
-// rec must stay alive until the stream has been synchronised (render_dev does).
-int tile_items(rt_ctx* c, const std::vector<rttile::Rec>& rec, int tiles_x, int rows, int width, int fb_count, uint4* ntile_dev,
-               uint32_t* perm_dev) {
-  HIPCHK(c, hipMemcpyAsync(ntile_dev, rec.data(), rec.size() * sizeof(uint4), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(tile_items_kernel, dim3((unsigned)rec.size()), dim3(256), 0, c->stream, ntile_dev, tiles_x, rows, width,
-                     fb_count, perm_dev);
-  HIPCHK(c, hipGetLastError());
-  return RT_OK;
-}
-
-void add_counters(rt_counters& t, const rt_counters& x) {
-  t.segments += x.segments;
-  t.node_tests += x.node_tests;
-  t.prim_tests += x.prim_tests;
-  t.samples += x.samples;
-  t.fallbacks += x.fallbacks;
-}
-
-// adapt_measure_kernel over the active tiles (all = false; the retired tiles' entries are re-measured too
-// when they hold the counts of another threshold) or every tile, then the tile arrays to the host:
-// afterwards h_max / h_above are current for every tile at `threshold`.  map_dev may be null.
-int adapt_measure(rt_adapt* ad, float threshold, bool all, float* map_dev, bool timed) {
-  rt_ctx* c = ad->ctx;
-  const size_t tiles = (size_t)ad->tiles_x * ad->tiles_y;
-  if (!ad->have_measure || memcmp(&ad->measured, &threshold, sizeof(float)) != 0) all = true;  // counts of another threshold
-  const unsigned blocks = all ? (unsigned)tiles : (unsigned)ad->active.size();
-  if (timed) HIPCHK(c, hipEventRecord(ad->ev[2], c->stream));
-  if (blocks > 0) {
-    hipLaunchKernelGGL(adapt_measure_kernel, dim3(blocks), dim3(256), 0, c->stream, all ? (const uint4*)nullptr : ad->ntile,
-                       ad->tile_n, ad->s1, ad->s2, ad->tiles_x, ad->rows, ad->args.width, threshold, map_dev, ad->tile_max,
-                       ad->tile_above);
-    HIPCHK(c, hipGetLastError());
-  }
-  if (timed) {
-    HIPCHK(c, hipEventRecord(ad->ev[3], c->stream));
-    ad->retire_timed = true;
-  }
-  HIPCHK(c, hipMemcpyAsync(ad->h_max.data(), ad->tile_max, tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(ad->h_above.data(), ad->tile_above, tiles * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  ad->measured = threshold;
-  ad->have_measure = true;
-  return RT_OK;
-}
-
-// The active list as tile_items_kernel's records for launches of fb_count frame buffers, on the device.
-int adapt_list(rt_adapt* ad, int fb_count, unsigned long long* n_items) {
-  rt_ctx* c = ad->ctx;
-  *n_items = rttile::records(ad->active.data(), (int)ad->active.size(), ad->tiles_x, ad->rows, ad->args.width, fb_count,
-                          ad->ntile_host);
-  HIPCHK(c, hipMemcpyAsync(ad->ntile, ad->ntile_host.data(), ad->ntile_host.size() * sizeof(uint4), hipMemcpyHostToDevice,
-                           c->stream));
-  return RT_OK;
-}
-
-void adapt_report(const rt_adapt* ad, float threshold, rt_adapt_report* rep) {
-  const size_t tiles = (size_t)ad->tiles_x * ad->tiles_y;
-  rep->fbs = ad->args.fb_count;
-  rep->tiles_x = ad->tiles_x;
-  rep->tiles_y = ad->tiles_y;
-  rep->tiles_active = (int32_t)ad->active.size();
-  rep->pixels = (int64_t)ad->rows * ad->args.width;
-  rep->pixels_active = 0;
-  rep->pixel_fbs = 0;
-  rep->pixels_above = 0;
-  rep->threshold = threshold;
-  float mx = 0.0f;
-  for (size_t t = 0; t < tiles; ++t) {
-    int tw, th;
-    ntile_size((int)t, ad->tiles_x, ad->rows, ad->args.width, tw, th);
-    rep->pixel_fbs += (int64_t)tw * th * ad->n_t[t];
-    rep->pixels_above += ad->h_above[t];
-    mx = std::max(mx, ad->h_max[t]);
-  }
-  for (int32_t t : ad->active) {
-    int tw, th;
-    ntile_size(t, ad->tiles_x, ad->rows, ad->args.width, tw, th);
-    rep->pixels_active += (int64_t)tw * th;
-  }
-  rep->max_noise = mx;
-}
-
-}  // namespace
-
-extern "C" {
-
-int rt_render_tiles(rt_ctx* c, const rt_render_args* a, const int32_t* tiles, int32_t n_tiles, float* fb,
-                    rt_counters* counters) {
-  if (!c) return RT_ERR_ARG;
-  int rc = validate_args(c, a);
-  if (rc) return rc;
-  if (!fb) return fail(c, RT_ERR_ARG, "null fb");
-  if (!tiles || n_tiles <= 0) return fail(c, RT_ERR_ARG, "empty tile list");
-  const int rows = rt_owned_rows(a, nullptr);
-  if (rows <= 0) return fail(c, RT_ERR_ARG, "no rows owned");
-  const long long items = (long long)a->fb_count * rows * a->width;
-  if (items > (1LL << 31)) return fail(c, RT_ERR_ARG, "tile launch: more than 2^31 items (fb_count x owned rows x width)");
-  const int tiles_x = (a->width + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
-  const int tiles_y = (rows + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
-  const long long n_all = (long long)tiles_x * tiles_y;
-  if (n_tiles > n_all) return fail(c, RT_ERR_ARG, "tile list: a repeated tile id");
-  std::vector<uint8_t> seen((size_t)n_all, 0);
-  for (int k = 0; k < n_tiles; ++k) {
-    if (tiles[k] < 0 || tiles[k] >= n_all) return fail(c, RT_ERR_ARG, "tile list: id out of range");
-    if (seen[(size_t)tiles[k]]) return fail(c, RT_ERR_ARG, "tile list: a repeated tile id");
-    seen[(size_t)tiles[k]] = 1;
-  }
-  if (!c->have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
-  if (!c->states || c->states_n != (long long)a->width * a->height || c->states_seed != a->seed)
-    return fail(c, RT_ERR_STATE, "rt_render_init not called for this size/seed");
-  HIPCHK(c, hipSetDevice(c->device));
-  std::vector<rttile::Rec> rec;
-  TileLaunch tl{nullptr, rttile::records(tiles, n_tiles, tiles_x, rows, a->width, a->fb_count, rec)};
-  uint4* ntile = nullptr;
-  uint32_t* perm = nullptr;
-  float* tmp = nullptr;  // a host fb is staged in and out: the floats outside the listed tiles stay
-  const size_t fb_bytes = (size_t)items * 3 * sizeof(float);
-  const bool host_fb = !device_ptr(fb);
-  if (hipMalloc((void**)&ntile, rec.size() * sizeof(uint4)) != hipSuccess ||
-      hipMalloc((void**)&perm, (size_t)tl.n_items * sizeof(uint32_t)) != hipSuccess ||
-      (host_fb && hipMalloc((void**)&tmp, fb_bytes) != hipSuccess)) {
-    (void)hipGetLastError();
-    rc = fail(c, RT_ERR_NOMEM, "hipMalloc tile launch");
-  }
-  if (!rc && host_fb && hipMemcpy(tmp, fb, fb_bytes, hipMemcpyHostToDevice) != hipSuccess)
-    rc = fail(c, RT_ERR_HIP, "copy frame buffer to device");
-  if (!rc) rc = tile_items(c, rec, tiles_x, rows, a->width, a->fb_count, ntile, perm);
-  tl.perm = perm;
-  if (!rc) rc = render_dev(c, a, host_fb ? tmp : fb, counters, &tl);
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(c, RT_ERR_HIP, "tile launch");
-  if (!rc && host_fb && hipMemcpy(fb, tmp, fb_bytes, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(c, RT_ERR_HIP, "copy frame buffer to host");
-  if (ntile) (void)hipFree(ntile);
-  if (perm) (void)hipFree(perm);
-  if (tmp) (void)hipFree(tmp);
-  return rc;
-}
-
-int rt_adapt_destroy(rt_adapt* ad) {
-  if (!ad) return RT_ERR_ARG;
-  (void)hipSetDevice(ad->ctx->device);
-  (void)hipStreamSynchronize(ad->ctx->stream);
-  void* bufs[] = {ad->sums, ad->s1, ad->s2, ad->scratch, ad->perm, ad->ntile, ad->tile_n, ad->tile_max, ad->tile_above, ad->img};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  for (hipEvent_t e : ad->ev)
-    if (e) (void)hipEventDestroy(e);
-  delete ad;
-  return RT_OK;
-}
-
-int rt_adapt_create(rt_ctx* c, const rt_render_args* a, int32_t chunk_fbs, rt_adapt** out) {
-  if (!c) return RT_ERR_ARG;
-  if (!out) return fail(c, RT_ERR_ARG, "null adaptive accumulator pointer");
-  *out = nullptr;
-  if (!a) return fail(c, RT_ERR_ARG, "null args");
-  rt_render_args one = *a;
-  one.fb_count = 1;
-  const int rc = validate_args(c, &one);
-  if (rc) return rc;
-  if (chunk_fbs < 1) return fail(c, RT_ERR_ARG, "chunk_fbs < 1");
-  if (a->fb_first > INT32_MAX - chunk_fbs) return fail(c, RT_ERR_ARG, "fb range overflows");
-  const long long rows = rt_owned_rows(a, nullptr);
-  const long long per_fb = rows * a->width * 3;
-  if (per_fb <= 0) return fail(c, RT_ERR_ARG, "no rows owned");
-  if ((long long)chunk_fbs * rows * a->width > (1LL << 31)) return fail(c, RT_ERR_ARG, "chunk_fbs x owned rows x width > 2^31");
-  const long long tiles_x = (a->width + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
-  const long long tiles_y = (rows + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
-  if (tiles_x * tiles_y > INT32_MAX) return fail(c, RT_ERR_ARG, "adaptive accumulator: too many tiles");
-  if (!c->have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
-  HIPCHK(c, hipSetDevice(c->device));
-  rt_adapt* ad = new rt_adapt;
-  ad->ctx = c;
-  ad->args = *a;
-  ad->args.fb_count = 0;
-  ad->chunk = chunk_fbs;
-  ad->per_fb = per_fb;
-  ad->rows = (int)rows;
-  ad->tiles_x = (int)tiles_x;
-  ad->tiles_y = (int)tiles_y;
-  ad->scene_gen = c->scene_gen;
-  const size_t nv = (size_t)per_fb, tiles = (size_t)(tiles_x * tiles_y);
-  ad->n_t.assign(tiles, 0);
-  ad->h_max.assign(tiles, 0.0f);
-  ad->h_above.assign(tiles, 0);
-  ad->active.resize(tiles);
-  for (size_t t = 0; t < tiles; ++t) ad->active[t] = (int32_t)t;
-  bool ok = hipMalloc((void**)&ad->sums, nv * sizeof(float)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&ad->s1, nv * sizeof(uint32_t)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&ad->s2, nv * sizeof(unsigned long long)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&ad->ntile, tiles * sizeof(uint4)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&ad->tile_n, tiles * sizeof(int32_t)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&ad->tile_max, tiles * sizeof(float)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&ad->tile_above, tiles * sizeof(int32_t)) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    rt_adapt_destroy(ad);
-    return fail(c, RT_ERR_NOMEM, "hipMalloc adaptive accumulator");
-  }
-  for (hipEvent_t& e : ad->ev)
-    if (ok && hipEventCreate(&e) != hipSuccess) {
-      e = nullptr;
-      ok = false;
-    }
-  ok = ok && hipMemsetAsync(ad->sums, 0, nv * sizeof(float), c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(ad->s1, 0, nv * sizeof(uint32_t), c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(ad->s2, 0, nv * sizeof(unsigned long long), c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(ad->tile_n, 0, tiles * sizeof(int32_t), c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(ad->tile_max, 0, tiles * sizeof(float), c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(ad->tile_above, 0, tiles * sizeof(int32_t), c->stream) == hipSuccess;
-  if (!ok) {
-    rt_adapt_destroy(ad);
-    return fail(c, RT_ERR_HIP, "set up adaptive accumulator");
-  }
-  *out = ad;
-  return RT_OK;
-}
-
-int rt_adapt_add(rt_adapt* ad, int32_t count, rt_counters* counters) {
-  if (!ad) return RT_ERR_ARG;
-  rt_ctx* c = ad->ctx;
-  rt_render_args& a = ad->args;
-  if (count < 1) return fail(c, RT_ERR_ARG, "count < 1");
-  if (count > INT32_MAX - a.fb_first - a.fb_count) return fail(c, RT_ERR_ARG, "fb range overflows");
-  if (count > rtacc::kNoiseMaxFbs - a.fb_count) return fail(c, RT_ERR_ARG, "noise monitor: more than 32768 frame buffers");
-  if (ad->scene_gen != c->scene_gen) return fail(c, RT_ERR_STATE, "scene uploaded again since the accumulator was created");
-  rt_counters total = {};
-  if (ad->active.empty()) {  // every tile has retired: nothing is rendered
-    if (counters) *counters = total;
-    return RT_OK;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!c->states || c->states_n != (long long)a.width * a.height || c->states_seed != a.seed) {
-    const int rc = rt_render_init(c, a.width, a.height, a.seed);
-    if (rc) return rc;
-  }
-  if (!ad->scratch) {
-    const size_t px = (size_t)ad->chunk * ad->rows * a.width;
-    if (hipMalloc((void**)&ad->scratch, px * 3 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&ad->perm, px * sizeof(uint32_t)) != hipSuccess) {
-      (void)hipGetLastError();
-      if (ad->scratch) (void)hipFree(ad->scratch);
-      ad->scratch = nullptr;
-      return fail(c, RT_ERR_NOMEM, "hipMalloc adaptive frame buffers");
-    }
-  }
-  for (int32_t left = count; left > 0;) {
-    const int32_t n = std::min(left, ad->chunk);
-    rt_render_args r = a;
-    r.fb_first = a.fb_first + a.fb_count;
-    r.fb_count = n;
-    TileLaunch tl{ad->perm, 0};
-    int rc = adapt_list(ad, n, &tl.n_items);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tile_items_kernel, dim3((unsigned)ad->active.size()), dim3(256), 0, c->stream, ad->ntile, ad->tiles_x,
-                       ad->rows, a.width, n, ad->perm);
-    HIPCHK(c, hipGetLastError());
-    rt_counters cnt = {};
-    if ((rc = render_dev(c, &r, ad->scratch, &cnt, &tl))) return rc;
-    HIPCHK(c, hipEventRecord(ad->ev[0], c->stream));
-    hipLaunchKernelGGL(adapt_fold_kernel, dim3((unsigned)ad->active.size()), dim3(256), 0, c->stream, ad->ntile, ad->tiles_x,
-                       ad->rows, a.width, ad->scratch, ad->per_fb, n, ad->sums, ad->s1, ad->s2);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ad->ev[1], c->stream));
-    ad->add_timed = true;
-    a.fb_count += n;
-    add_counters(total, cnt);
-    left -= n;
-  }
-  for (int32_t t : ad->active) ad->n_t[(size_t)t] = a.fb_count;
-  HIPCHK(c, hipMemcpyAsync(ad->tile_n, ad->n_t.data(), ad->n_t.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (counters) *counters = total;
-  return RT_OK;
-}
-
-int rt_adapt_retire(rt_adapt* ad, float threshold, int32_t max_above, rt_adapt_report* rep) {
-  if (!ad) return RT_ERR_ARG;
-  rt_ctx* c = ad->ctx;
-  if (max_above < 0) return fail(c, RT_ERR_ARG, "max_above < 0");
-  if (ad->args.fb_count < 2) return fail(c, RT_ERR_STATE, "noise needs at least 2 frame buffers");
-  HIPCHK(c, hipSetDevice(c->device));
-  unsigned long long unused = 0;
-  int rc = adapt_list(ad, 1, &unused);  // the measure kernel reads the ids only
-  if (!rc) rc = adapt_measure(ad, threshold, false, nullptr, true);
-  if (rc) return rc;
-  std::vector<int32_t> keep;
-  for (int32_t t : ad->active)
-    if (ad->h_above[(size_t)t] > max_above) keep.push_back(t);
-  ad->active.swap(keep);  // retiring is final: n_t of the others stays at fbs
-  if (rep) adapt_report(ad, threshold, rep);
-  return RT_OK;
-}
-
-int rt_adapt_get_report(rt_adapt* ad, float threshold, rt_adapt_report* rep) {
-  if (!ad) return RT_ERR_ARG;
-  rt_ctx* c = ad->ctx;
-  if (!rep) return fail(c, RT_ERR_ARG, "null report");
-  if (ad->args.fb_count < 2) return fail(c, RT_ERR_STATE, "noise needs at least 2 frame buffers");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int rc = adapt_measure(ad, threshold, true, nullptr, false);
-  if (rc) return rc;
-  adapt_report(ad, threshold, rep);
-  return RT_OK;
-}
-
-int rt_adapt_counts(rt_adapt* ad, int32_t* tile_fbs) {
-  if (!ad) return RT_ERR_ARG;
-  if (!tile_fbs) return fail(ad->ctx, RT_ERR_ARG, "null counts");
-  std::copy(ad->n_t.begin(), ad->n_t.end(), tile_fbs);
-  return RT_OK;
-}
-
-int rt_adapt_noise_map(rt_adapt* ad, float* out) {
-  if (!ad) return RT_ERR_ARG;
-  rt_ctx* c = ad->ctx;
-  if (!out) return fail(c, RT_ERR_ARG, "null map");
-  if (ad->args.fb_count < 2) return fail(c, RT_ERR_STATE, "noise needs at least 2 frame buffers");
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t bytes = (size_t)ad->rows * ad->args.width * sizeof(float);
-  float* tmp = nullptr;  // a host map is staged through device memory
-  if (!device_ptr(out) && hipMalloc((void**)&tmp, bytes) != hipSuccess) return fail(c, RT_ERR_NOMEM, "hipMalloc noise map");
-  int rc = adapt_measure(ad, ad->have_measure ? ad->measured : 0.0f, true, tmp ? tmp : out, false);
-  if (!rc && tmp && hipMemcpy(out, tmp, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(c, RT_ERR_HIP, "copy noise map");
-  if (tmp) (void)hipFree(tmp);
-  return rc;
-}
-
-int rt_adapt_image(rt_adapt* ad, uint8_t* out, int32_t png_order) {
-  if (!ad) return RT_ERR_ARG;
-  rt_ctx* c = ad->ctx;
-  if (!out) return fail(c, RT_ERR_ARG, "null image");
-  if (png_order != 0 && png_order != 1) return fail(c, RT_ERR_ARG, "bad png_order");
-  const rt_render_args& a = ad->args;
-  HIPCHK(c, hipSetDevice(c->device));
-  const bool out_dev = device_ptr(out);
-  if (png_order && ad->per_fb != (long long)a.width * a.height * 3)
-    return fail(c, RT_ERR_ARG, "png_order needs the whole-image tiling");
-  if (png_order && out_dev) return fail(c, RT_ERR_ARG, "png_order needs a host image");
-  if (a.fb_count < 1) return fail(c, RT_ERR_STATE, "no frame buffer accumulated yet");
-  if (!out_dev && !ad->img && hipMalloc((void**)&ad->img, (size_t)ad->per_fb) != hipSuccess) {
-    ad->img = nullptr;
-    return fail(c, RT_ERR_NOMEM, "hipMalloc adaptive image");
-  }
-  uint8_t* img = out_dev ? out : ad->img;
-  const long long px = ad->per_fb / 3;
-  hipLaunchKernelGGL(adapt_image_kernel, dim3((unsigned)((px + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, ad->sums,
-                     ad->tile_n, ad->tiles_x, ad->rows, a.width, img);
-  HIPCHK(c, hipGetLastError());
-  if (out_dev) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RT_OK;
-  }
-  if (!png_order) {
-    HIPCHK(c, hipMemcpyAsync(out, img, (size_t)ad->per_fb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RT_OK;
-  }
-  std::vector<uint8_t> tmp((size_t)ad->per_fb);
-  HIPCHK(c, hipMemcpyAsync(tmp.data(), img, tmp.size(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const size_t row = (size_t)a.width * 3;
-  for (int j = 0; j < a.height; ++j) memcpy(out + (size_t)(a.height - 1 - j) * row, tmp.data() + j * row, row);
-  return RT_OK;
-}
-
-float rt_adapt_last_add_ms(const rt_adapt* ad) {
-  float ms = 0.0f;
-  if (!ad || !ad->add_timed || hipEventElapsedTime(&ms, ad->ev[0], ad->ev[1]) != hipSuccess) return 0.0f;
-  return ms;
-}
-float rt_adapt_last_retire_ms(const rt_adapt* ad) {
-  float ms = 0.0f;
-  if (!ad || !ad->retire_timed || hipEventElapsedTime(&ms, ad->ev[2], ad->ev[3]) != hipSuccess) return 0.0f;
-  return ms;
-}
-
-}  // extern "C"

@@ -7,7 +7,7 @@
 //   96              u64[n_values]  S2 = sum of c^4
 //   96 + 8 n_values u32[n_values]  S1 = sum of c^2        (c = quant(fb[f][k]), owned rows ascending)
 //
-// The measure is the one of noise_measure_kernel (rt_kernels.hip), tile for tile; rt_hip.h has the
+// The measure is the one of noise_measure_kernel (rt_progressive.hip), tile for tile; rt_hip.h has the
 // definitions and the bound that keeps every integer below 2^64.
 #include "rt_accum_blob.h"
 

@@ -28,49 +28,22 @@ inline void size(int id, int tiles_x, int rows, int width, int& tw, int& th) {
   th = std::min(kTile, rows - ty * kTile);
 }
 
-// Item order of a tile launch.  Tile-major (shipped): the listed tiles one after another, inside a tile
-// one frame buffer after another, inside that the tile's pixels row by row -- adjacent claims are
-// neighbouring pixels of one frame buffer.  Row-major: ascending items, rt_render's own order
-// restricted to the list.  Measured against each other in DESIGN.md 3.6; the other order stays for
-// that measurement (-DRT_TILE_ORDER_ROW_MAJOR=1).
-#ifndef RT_TILE_ORDER_ROW_MAJOR
-#define RT_TILE_ORDER_ROW_MAJOR 0
-#endif
-
+// Item order of a tile launch, tile-major: the listed tiles one after another, inside a tile one frame
+// buffer after another, inside that the tile's pixels row by row -- adjacent claims are neighbouring
+// pixels of one frame buffer.  (Measured against ascending items, rt_render's own order restricted to the
+// list)
+//
 // The records of the listed tiles (distinct ids inside the grid; fb_count x rows x width <= 2^31) and
 // the item count: the positions the records describe are a permutation of 0 .. count - 1.
 inline unsigned long long records(const int32_t* tiles, int n_tiles, int tiles_x, int rows, int width, int fb_count,
-                                  std::vector<Rec>& rec, bool row_major = RT_TILE_ORDER_ROW_MAJOR != 0) {
+                                  std::vector<Rec>& rec) {
   rec.resize((size_t)n_tiles);
   unsigned long long pixels = 0;
-  if (row_major) {
-    // per tile row: the listed tiles' columns side by side, every (row, fb) one run
-    std::vector<int32_t> sorted(tiles, tiles + n_tiles);
-    std::sort(sorted.begin(), sorted.end());
-    for (int k = 0; k < n_tiles;) {
-      const int ty = sorted[k] / tiles_x;
-      int e = k, roww = 0, tw = 0, th = 0;
-      for (; e < n_tiles && sorted[e] / tiles_x == ty; ++e) {
-        size(sorted[e], tiles_x, rows, width, tw, th);
-        roww += tw;
-      }
-      unsigned off = 0;
-      for (int q = k; q < e; ++q) {
-        size(sorted[q], tiles_x, rows, width, tw, th);
-        rec[(size_t)q] = Rec{(uint32_t)sorted[q], (uint32_t)(pixels * fb_count + off), (uint32_t)roww * (uint32_t)fb_count,
-                             (uint32_t)roww};
-        off += (unsigned)tw;
-      }
-      pixels += (unsigned long long)roww * th;
-      k = e;
-    }
-  } else {
-    for (int k = 0; k < n_tiles; ++k) {
-      int tw, th;
-      size(tiles[k], tiles_x, rows, width, tw, th);
-      rec[(size_t)k] = Rec{(uint32_t)tiles[k], (uint32_t)(pixels * fb_count), (uint32_t)tw, (uint32_t)(tw * th)};
-      pixels += (unsigned long long)tw * th;
-    }
+  for (int k = 0; k < n_tiles; ++k) {
+    int tw, th;
+    size(tiles[k], tiles_x, rows, width, tw, th);
+    rec[(size_t)k] = Rec{(uint32_t)tiles[k], (uint32_t)(pixels * fb_count), (uint32_t)tw, (uint32_t)(tw * th)};
+    pixels += (unsigned long long)tw * th;
   }
   return pixels * (unsigned long long)fb_count;
 }

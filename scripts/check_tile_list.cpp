@@ -1,8 +1,8 @@
 // check_tile_list.cpp -- csrc/rt_tile_list.h on the CPU: tile_items_kernel's index arithmetic replayed
-// over the records of rttile::records for both item orders, many shapes and tile subsets.  Checks that
-// every written position is inside the item list (the kernel's only store), that the positions are a
-// permutation, that the items are exactly the (row, fb, column) triples of the listed tiles, and the
-// order each mode promises.  Stand-alone (own main); built by tests/test_adapt_cpu.py with g++, and
+// over the records of rttile::records, many shapes and tile subsets.  Checks that every written position
+// is inside the item list (the kernel's only store), that the positions are a permutation, that the items
+// are exactly the (row, fb, column) triples of the listed tiles, and the tile-major order: a tile's pixels
+// of one frame buffer in one run.  Stand-alone (own main); built by tests/test_adapt_cpu.py with g++, and
 // run once by hand under -fsanitize=address,undefined:
 //   g++ -std=c++17 -g -fsanitize=address,undefined -I raytracing_gpu_amd/csrc scripts/check_tile_list.cpp -o /tmp/ctl && /tmp/ctl
 #include <cstdio>
@@ -26,10 +26,10 @@ int failures = 0;
     }                                   \
   } while (0)
 
-void run(int rows, int width, int fb_count, const std::vector<int32_t>& tiles, bool row_major) {
+void run(int rows, int width, int fb_count, const std::vector<int32_t>& tiles) {
   const int tiles_x = (width + 15) / 16;
   std::vector<rttile::Rec> rec;
-  const unsigned long long n = rttile::records(tiles.data(), (int)tiles.size(), tiles_x, rows, width, fb_count, rec, row_major);
+  const unsigned long long n = rttile::records(tiles.data(), (int)tiles.size(), tiles_x, rows, width, fb_count, rec);
   unsigned long long want = 0;
   std::vector<uint8_t> listed((size_t)tiles_x * ((rows + 15) / 16), 0);
   for (int32_t t : tiles) {
@@ -72,8 +72,7 @@ void run(int rows, int width, int fb_count, const std::vector<int32_t>& tiles, b
     CHECK(listed[(size_t)(q / 16) * tiles_x + i / 16], "item %u is in no listed tile", item);
     CHECK(!seen[item], "item %u twice", item);
     seen[item] = 1;
-    if (row_major && p > 0) CHECK(perm[(size_t)p - 1] < item, "row-major list not ascending at %llu", p);
-    if (!row_major && p > 0 && perm[(size_t)p - 1] != kUnset) {  // a tile's pixels of one fb are one run
+    if (p > 0 && perm[(size_t)p - 1] != kUnset) {  // a tile's pixels of one fb are one run
       const uint32_t prev = perm[(size_t)p - 1];
       const int pq = (int)(prev / per_row), pf = (int)((prev - (long long)pq * per_row) / width),
                 pi = (int)(prev - (long long)pq * per_row - (long long)pf * width);
@@ -91,38 +90,35 @@ int main() {
   const int shapes[][2] = {{37, 70}, {48, 80}, {17, 70}, {1, 1}, {16, 16}, {17, 17}, {5, 300}, {300, 5}, {33, 31}};
   long long cases = 0;
   for (const auto& s : shapes)
-    for (int fb_count : {1, 3, 10})
-      for (int mode = 0; mode < 2; ++mode) {
-        const int rows = s[0], width = s[1];
-        const int n_all = ((rows + 15) / 16) * ((width + 15) / 16);
-        std::vector<int32_t> all((size_t)n_all);
-        for (int t = 0; t < n_all; ++t) all[(size_t)t] = t;
-        run(rows, width, fb_count, all, mode != 0);
-        run(rows, width, fb_count, {n_all - 1}, mode != 0);
-        run(rows, width, fb_count, {0}, mode != 0);
-        for (int trial = 0; trial < 8; ++trial) {  // random subsets in random order
-          std::vector<int32_t> pick = all;
-          std::shuffle(pick.begin(), pick.end(), rng);
-          pick.resize((size_t)(1 + rng() % (unsigned)n_all));
-          run(rows, width, fb_count, pick, mode != 0);
-          ++cases;
-        }
-        cases += 3;
+    for (int fb_count : {1, 3, 10}) {
+      const int rows = s[0], width = s[1];
+      const int n_all = ((rows + 15) / 16) * ((width + 15) / 16);
+      std::vector<int32_t> all((size_t)n_all);
+      for (int t = 0; t < n_all; ++t) all[(size_t)t] = t;
+      run(rows, width, fb_count, all);
+      run(rows, width, fb_count, {n_all - 1});
+      run(rows, width, fb_count, {0});
+      for (int trial = 0; trial < 16; ++trial) {  // random subsets in random order
+        std::vector<int32_t> pick = all;
+        std::shuffle(pick.begin(), pick.end(), rng);
+        pick.resize((size_t)(1 + rng() % (unsigned)n_all));
+        run(rows, width, fb_count, pick);
+        ++cases;
       }
+      cases += 3;
+    }
   // the largest list the ABI accepts: 2^31 items (records only; the list itself is not expanded)
   {
     const int rows = 32768, width = 32768, fb_count = 2;
     const int tiles_x = width / 16;
     std::vector<int32_t> all((size_t)tiles_x * (rows / 16));
     for (size_t t = 0; t < all.size(); ++t) all[t] = (int32_t)t;
-    for (int mode = 0; mode < 2; ++mode) {
-      std::vector<rttile::Rec> rec;
-      const unsigned long long n = rttile::records(all.data(), (int)all.size(), tiles_x, rows, width, fb_count, rec, mode != 0);
-      CHECK(n == (1ull << 31), "2^31 items: %llu", n);
-      const rttile::Rec& last = rec.back();
-      const unsigned long long top = (unsigned long long)last.base + 15ull * last.row_stride + (unsigned long long)(fb_count - 1) * last.fb_stride + 15;
-      CHECK(top == n - 1, "2^31 items: last position %llu", top);
-    }
+    std::vector<rttile::Rec> rec;
+    const unsigned long long n = rttile::records(all.data(), (int)all.size(), tiles_x, rows, width, fb_count, rec);
+    CHECK(n == (1ull << 31), "2^31 items: %llu", n);
+    const rttile::Rec& last = rec.back();
+    const unsigned long long top = (unsigned long long)last.base + 15ull * last.row_stride + (unsigned long long)(fb_count - 1) * last.fb_stride + 15;
+    CHECK(top == n - 1, "2^31 items: last position %llu", top);
   }
   if (failures) {
     fprintf(stderr, "%d failures\n", failures);

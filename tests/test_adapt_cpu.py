@@ -110,10 +110,10 @@ def test_model_does_not_depend_on_how_adds_are_split():
 
 
 # ---------------------------------------------------------------- the item list of a tile launch, on the CPU
-def test_tile_list_records_are_a_permutation_in_both_orders(tmp_path):
+def test_tile_list_records_are_a_permutation(tmp_path):
     """scripts/check_tile_list.cpp replays tile_items_kernel's index arithmetic over the host's records
     (csrc/rt_tile_list.h): every store lands inside the item list, the list is a permutation of the
-    listed tiles' items, in the order each mode promises."""
+    listed tiles' items, a tile's pixels of one frame buffer in one run."""
     hdr = open(os.path.join(ROOT, "raytracing_gpu_amd", "csrc", "rt_tile_list.h")).read()
     assert not re.search(r'#\s*include\s*[<"]hip', hdr)
     exe = tmp_path / "check_tile_list"

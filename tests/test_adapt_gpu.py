@@ -3,6 +3,7 @@ include/rt_hip.h): a tile launch writes rt_render's floats into the listed tiles
 counters partition rt_render's, it leaves the context's item schedule alone; the adaptive accumulator's
 tiles are the oracle's draw() at their own frame-buffer counts, it equals the numpy model of
 tests/adapt_ref.py in every integer, and its results do not depend on how the adds were grouped."""
+import ctypes
 import json
 import os
 import subprocess
@@ -323,6 +324,19 @@ def test_adaptive_equals_the_model(rtlib, gpu_ctx, scene, size, band, cam):
         print(scene, size, "threshold", thr, "counts", np.unique(model["counts"], return_counts=True))
         assert np.array_equal(ad.counts(), model["counts"])
         assert np.array_equal(ad.image(), model["image"])
+        if size == SMALL:  # rt_adapt_image's other outputs, through the C ABI
+            import torch
+
+            img = ad.image()
+            dev = torch.zeros(img.size + 1, dtype=torch.uint8, device="cuda")
+            assert dev.data_ptr() % 4 == 0
+            gpu_ctx._after_torch()
+            for o in (0, 1):  # into device memory, 4-byte aligned and one byte off it: the same image
+                assert rtlib.lib().rt_adapt_image(ad._h, ctypes.c_void_p(dev.data_ptr() + o), 0) == 0
+                assert np.array_equal(dev.cpu().numpy()[o:o + img.size].reshape(img.shape), img)
+            assert rtlib.lib().rt_adapt_image(ad._h, ctypes.c_void_p(dev.data_ptr()), 1) == RT_ERR_ARG  # png order + device
+            if band:  # png order needs the whole-image tiling
+                assert _status(rtlib, lambda: ad.image(png_order=True)) == RT_ERR_ARG
         for got, want in zip(reports, model["reports"]):
             for k in want:
                 if k == "max_noise":
