@@ -29,6 +29,12 @@
 //     --min-fbs F           noise above T.  Each step prints one JSON line with "fbs", "tiles_active",
 //                           "pixel_fbs" and "noise_max"; a last line carries "stopped_at" and "pixel_fbs".
 //                           Ends when no tile is active or at NO_FB.  Not with --progressive / --checkpoint
+//     --adaptive-checkpoint FILE   with --adaptive: save the rt_adapt to FILE after every step and, when FILE
+//                           exists, continue from it (prints a JSON line with "resumed_from")
+//     --dilate R            with --adaptive: a tile that passes stays active while an active tile within R
+//                           tiles of it (Chebyshev) fails (default 0)
+//     --reopen              with --adaptive: on resuming, make the tiles that fail T / M, and those within R
+//                           of one, active again, each from its own count (prints a line with "reopened")
 //
 // Writes OUT.ppm (binary P6, top row first) and one JSON line per draw on stdout.  Files written
 // more than once go to a temporary name first and are renamed into place.
@@ -184,26 +190,75 @@ int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int
   return 0;
 }
 
-// draw() through an adaptive accumulator: `step` frame buffers at a time for the tiles still active.
+// draw() through an adaptive accumulator: `step` frame buffers at a time for the tiles still active, none
+// beyond NO_FB; with a checkpoint the state is saved after every step and an existing one is continued.
 int draw_adaptive(rt_ctx* ctx, const char* name, const rt_render_args& a, int step, const char* out,
-                  std::vector<uint8_t>& png, float noise_t, int max_above, int min_fbs) {
+                  std::vector<uint8_t>& png, float noise_t, int max_above, int min_fbs, const char* ckpt, int dilate,
+                  bool reopen) {
   rt_adapt* ad = nullptr;
-  if (rt_adapt_create(ctx, &a, step, &ad)) return die("rt_adapt_create", rt_last_error(ctx));
+  rt_adapt_report rep = {};
+  int done = 0;
+  bool measured = false;  // rep describes the current state
+  std::vector<unsigned char> blob;
+  if (ckpt && read_file(ckpt, blob)) {
+    rt_accum_info i = {};
+    if (rt_adaptive_load(ctx, blob.data(), blob.size(), step, &ad)) return die("rt_adaptive_load", rt_last_error(ctx));
+    rt_adaptive_blob_info(blob.data(), blob.size(), &i);
+    const rt_render_args& b = i.args;
+    if (b.width != a.width || b.height != a.height || b.spp != a.spp || b.fb_first != a.fb_first ||
+        b.max_depth != a.max_depth || b.cam_mode != a.cam_mode || b.band_rows != a.band_rows ||
+        b.band_first != a.band_first || b.band_stride != a.band_stride || b.seed != a.seed || b.fb_count > a.fb_count)
+      return die("checkpoint", "belongs to a draw with other settings");
+    done = b.fb_count;
+    printf("{\"resumed_from\": %d, \"checkpoint\": \"%s\"}\n", done, ckpt);
+    if (reopen && done >= 2) {
+      int before = 0;
+      if (rt_adapt_get_report(ad, noise_t, &rep)) return die("rt_adapt_get_report", rt_last_error(ctx));
+      before = rep.tiles_active;
+      if (rt_adaptive_reopen(ad, noise_t, max_above, dilate, &rep)) return die("rt_adaptive_reopen", rt_last_error(ctx));
+      measured = true;
+      printf("{\"reopened\": %d, \"tiles_active\": %d, \"until_noise\": %.9g}\n", rep.tiles_active - before, rep.tiles_active,
+             noise_t);
+    }
+    fflush(stdout);
+  } else if (rt_adapt_create(ctx, &a, step, &ad)) {
+    return die("rt_adapt_create", rt_last_error(ctx));
+  }
   char head[64];
   snprintf(head, sizeof(head), "P6\n%d %d\n255\n", a.width, a.height);
-  rt_adapt_report rep = {};
-  rep.tiles_active = 1;
-  int done = 0;
-  while (done < a.fb_count && rep.tiles_active > 0) {
+  const size_t tiles = (size_t)((a.width + 15) / 16) * (size_t)((a.height + 15) / 16);
+  std::vector<int32_t> counts(tiles);
+  std::vector<uint8_t> flags(tiles);
+  // a step can still render: some active tile is below NO_FB; done = the largest count
+  auto more = [&]() {
+    rt_adapt_counts(ad, counts.data());
+    rt_adaptive_active(ad, flags.data());
+    bool any = false;
+    for (size_t t = 0; t < tiles; ++t) {
+      done = std::max(done, (int)counts[t]);
+      any = any || (flags[t] && counts[t] < a.fb_count);
+    }
+    return any;
+  };
+  bool stepped = false;
+  while (more()) {
     const auto t0 = std::chrono::steady_clock::now();
     rt_counters c = {};
-    const int n = std::min(step, a.fb_count - done);
-    if (rt_adapt_add(ad, n, &c)) return die("rt_adapt_add", rt_last_error(ctx));
-    done += n;
+    if (rt_adaptive_add(ad, step, a.fb_count, &c)) return die("rt_adaptive_add", rt_last_error(ctx));
+    stepped = true;
+    (void)more();
     const bool retire = done >= std::max(2, min_fbs);
-    if (retire && rt_adapt_retire(ad, noise_t, max_above, &rep)) return die("rt_adapt_retire", rt_last_error(ctx));
+    if (retire && rt_adaptive_retire(ad, noise_t, max_above, dilate, &rep)) return die("rt_adaptive_retire", rt_last_error(ctx));
+    measured = retire;
     if (rt_adapt_image(ad, png.data(), 1)) return die("rt_adapt_image", rt_last_error(ctx));
     if (!write_file(out, head, png.data(), png.size())) return die("write", out);
+    if (ckpt) {
+      size_t need = 0;
+      rt_adaptive_save(ad, nullptr, 0, &need);
+      blob.resize(need);
+      if (rt_adaptive_save(ad, blob.data(), blob.size(), nullptr)) return die("rt_adaptive_save", rt_last_error(ctx));
+      if (!write_file(ckpt, "", blob.data(), blob.size())) return die("write", ckpt);
+    }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     printf("{\"fbs\": %d, \"scene\": \"%s\", \"width\": %d, \"height\": %d, \"wall_ms\": %.3f, \"segments\": %llu, "
            "\"samples\": %llu",
@@ -214,9 +269,14 @@ int draw_adaptive(rt_ctx* ctx, const char* name, const rt_render_args& a, int st
     printf("}\n");
     fflush(stdout);
   }
-  const long long pixel_fbs = done >= std::max(2, min_fbs) ? (long long)rep.pixel_fbs : (long long)a.width * a.height * done;
+  if (!stepped && done > 0) {  // a resumed draw with nothing left to render still leaves its image
+    if (rt_adapt_image(ad, png.data(), 1)) return die("rt_adapt_image", rt_last_error(ctx));
+    if (!write_file(out, head, png.data(), png.size())) return die("write", out);
+    if (!measured && done >= 2 && rt_adapt_get_report(ad, noise_t, &rep) == 0) measured = true;
+  }
+  const long long pixel_fbs = measured ? (long long)rep.pixel_fbs : (long long)a.width * a.height * done;
   printf("{\"stopped_at\": %d, \"pixel_fbs\": %lld, \"tiles_active\": %d, \"until_noise\": %.9g, \"max_above\": %d}\n", done,
-         pixel_fbs, done >= std::max(2, min_fbs) ? rep.tiles_active : -1, noise_t, max_above);
+         pixel_fbs, measured ? rep.tiles_active : -1, noise_t, max_above);
   fflush(stdout);
   rt_adapt_destroy(ad);
   return 0;
@@ -228,7 +288,8 @@ int main(int argc, char** argv) {
   if (argc < 6) {
     fprintf(stderr, "usage: rt_main SCENE WIDTH SPP_PER_FB NO_FB OUT.ppm [--devices 0,1] [--gather rccl|host] "
                     "[--band-rows B] [--repeat K] [--depth D] [--height H] [--obj PATH] [--tex PATH] [--progressive K] [--checkpoint FILE] "
-                    "[--until-noise T [--noisy-fraction F]] [--adaptive K --until-noise T [--max-above M] [--min-fbs F]]\n");
+                    "[--until-noise T [--noisy-fraction F]] [--adaptive K --until-noise T [--max-above M] [--min-fbs F] "
+                    "[--adaptive-checkpoint FILE] [--dilate R] [--reopen]]\n");
     return 2;
   }
   const char* name = argv[1];
@@ -239,7 +300,9 @@ int main(int argc, char** argv) {
   const char* out = argv[5];
   std::vector<int> devices;
   int gather = RT_GATHER_RCCL, band_rows = 4, repeat = 1;
-  const char *obj_path = nullptr, *tex_path = nullptr, *ckpt_path = nullptr;
+  const char *obj_path = nullptr, *tex_path = nullptr, *ckpt_path = nullptr, *adaptive_ckpt = nullptr;
+  int dilate = 0;
+  bool reopen = false, have_resume_opts = false;
   int height = 0;
   int progressive = 0, adaptive = 0, max_above = 0, min_fbs = 4;
   bool have_adaptive = false, have_adaptive_opts = false;
@@ -262,6 +325,9 @@ int main(int argc, char** argv) {
     else if (a == "--adaptive") have_adaptive = true, adaptive = atoi(v), ++k;
     else if (a == "--max-above") have_adaptive_opts = true, max_above = atoi(v), ++k;
     else if (a == "--min-fbs") have_adaptive_opts = true, min_fbs = atoi(v), ++k;
+    else if (a == "--adaptive-checkpoint") have_resume_opts = true, adaptive_ckpt = v, ++k;
+    else if (a == "--dilate") have_resume_opts = true, dilate = atoi(v), ++k;
+    else if (a == "--reopen") have_resume_opts = true, reopen = true;
     else if (a == "--until-noise") until_noise = true, noise_t = (float)atof(v), ++k;
     else if (a == "--noisy-fraction") have_fraction = true, noisy_fraction = atof(v), ++k;
     else return die("unknown option", argv[k]);
@@ -273,6 +339,9 @@ int main(int argc, char** argv) {
     if (!until_noise) return die("--adaptive", "needs --until-noise T");
     if (adaptive < 1 || s.no_fb < 1) return die("--adaptive", "K and NO_FB must be at least 1");
     if (max_above < 0) return die("--max-above", "must be at least 0");
+    if (dilate < 0) return die("--dilate", "must be at least 0");
+  } else if (have_resume_opts) {
+    return die("--adaptive-checkpoint / --dilate / --reopen", "need --adaptive K");
   } else if (have_adaptive_opts) {
     return die("--max-above / --min-fbs", "need --adaptive K");
   }
@@ -339,7 +408,7 @@ int main(int argc, char** argv) {
   }
   if (have_adaptive) {
     if (!ctx) return die("--adaptive", "one GPU only (no --devices)");
-    const int rc = draw_adaptive(ctx, name, a, adaptive, out, png, noise_t, max_above, min_fbs);
+    const int rc = draw_adaptive(ctx, name, a, adaptive, out, png, noise_t, max_above, min_fbs, adaptive_ckpt, dilate, reopen);
     rt_ctx_destroy(ctx);
     rt_scene_free(scene);
     return rc;

@@ -498,8 +498,8 @@ int rt_render_tiles(rt_ctx* ctx, const rt_render_args* args, const int32_t* tile
 
 /* ------------------------------------------------------------------ adaptive accumulator */
 /* A progressive draw that stops rendering a tile (as above) once the tile's own noise estimate is low
- * enough, and goes on with the others.  An object of its own beside rt_accum (no checkpoint format, no
- * rt_multi support).  Per accumulator value it keeps the float sum of rt_accum (the same operations in
+ * enough, and goes on with the others.  An object of its own beside rt_accum (no rt_multi support; its
+ * checkpoint, reopening and dilation are the rt_adaptive_* functions below).  Per accumulator value it keeps the float sum of rt_accum (the same operations in
  * the same order) and the integer moments S1, S2 of rt_noise: 16 bytes per value; per tile n_t, the
  * number of frame buffers folded into it; and, from the first add, a scratch of chunk_fbs frame buffers
  * with the item list of its launches.
@@ -512,8 +512,9 @@ int rt_render_tiles(rt_ctx* ctx, const rt_render_args* args, const int32_t* tile
  *
  * What it does not give: stopping a tile on the spread of its own samples biases it slightly, towards
  * stopping while it happens to look smooth (a rare bright path that has not occurred yet cannot show in
- * the spread).  The only guard is the caller's: do not retire before enough frame buffers (min_fbs of
- * the Python driver).  The reference has no adaptive mode to compare with. */
+ * the spread).  The guards are the caller's: do not retire before enough frame buffers (min_fbs of the
+ * Python driver), and keep the neighbours of a noisy tile active (dilate of rt_adaptive_retire).  The
+ * reference has no adaptive mode to compare with. */
 typedef struct rt_adapt rt_adapt;
 typedef struct rt_adapt_report {
   int32_t fbs;            /* frame buffers rendered for the tiles still active (= max n_t)       */
@@ -531,12 +532,12 @@ int rt_adapt_create(rt_ctx* ctx, const rt_render_args* args, int32_t chunk_fbs, 
  * per launch) and folds them in; the fold's traffic is the active tiles'.  counters (may be NULL)
  * receives this call's totals.  With no active tile it renders nothing, zeroes counters and returns
  * RT_OK.  RT_ERR_ARG, before anything is rendered, when fbs + count would exceed rt_noise's 32 768;
- * RT_ERR_STATE after another rt_scene_upload. */
+ * RT_ERR_STATE after another rt_scene_upload.  Otherwise rt_adaptive_add with limit = 32 768. */
 int rt_adapt_add(rt_adapt* ad, int32_t count, rt_counters* counters);
 /* Needs fbs >= 2 (RT_ERR_STATE otherwise).  For every active tile: the per-pixel noise by rt_noise's
  * definition with n = n_t (the same device code), and the tile retires when at most max_above (>= 0) of
- * its pixels have noise > threshold.  Retiring is final: a retired tile is never rendered again and its
- * n_t stays.  rep (may be NULL) describes the state after retiring; max_noise and pixels_above cover all
+ * its pixels have noise > threshold.  A retired tile is not rendered again and its n_t stays, unless
+ * rt_adaptive_reopen makes it active again.  rt_adaptive_retire with dilate = 0.  rep (may be NULL) describes the state after retiring; max_noise and pixels_above cover all
  * tiles, retired ones at their frozen n_t.  Only maxima and integer counts are reduced. */
 int rt_adapt_retire(rt_adapt* ad, float threshold, int32_t max_above, rt_adapt_report* rep);
 /* rt_accum_image's conventions; quant(sum / n_t) per pixel.  RT_ERR_STATE before the first frame buffer. */
@@ -553,6 +554,66 @@ int rt_adapt_get_report(rt_adapt* ad, float threshold, rt_adapt_report* rep);
 float rt_adapt_last_add_ms(const rt_adapt* ad);
 float rt_adapt_last_retire_ms(const rt_adapt* ad);
 int rt_adapt_destroy(rt_adapt* ad);
+
+/* ---- checkpoint and resume, reopening retired tiles, dilation: further calls on an rt_adapt (their prefix
+ * differs only because the rt_adapt_ family is closed).  None of them weakens the guarantee above: tile t
+ * of the image stays byte-identical to rt_draw with no_fb = n_t, and the n_t stay an output.
+ *
+ * dilate = r >= 0 (negative: RT_ERR_ARG) is a Chebyshev radius in tiles over the tile grid, that is over
+ * (owned-row index, column): tile (ty, tx) is within r of (uy, ux) when max(|ty - uy|, |tx - ux|) <= r.
+ * For a band tiling the neighbours are therefore neighbours in the list of owned rows, not in the image:
+ * two tile rows that are adjacent in the grid may lie band_stride bands apart.  dilate_r(F) is the set of
+ * tiles within r of a tile of F; dilate_0(F) = F.
+ *
+ * rt_adaptive_retire: rt_adapt_retire with dilation.  With F = the active tiles that have more than
+ * max_above pixels of noise > threshold, the active set becomes its intersection with dilate_r(F): a passing tile within
+ * r of a failing active tile stays active (it is the neighbour most likely to look smooth by chance).  When
+ * no active tile fails every tile retires, so a draw still ends.
+ *
+ * rt_adaptive_reopen: needs fbs >= 2 (RT_ERR_STATE otherwise).  Every tile, active or retired, is measured
+ * at its own n_t; with F = all the tiles that fail, the active set becomes its union with dilate_r(F).  It never
+ * retires a tile.  A reopened tile keeps its n_t, its sums and its moments and continues from frame buffer
+ * fb_first + n_t, exactly where it stopped.  rep follows rt_adapt_retire's conventions (fbs = max n_t).
+ *
+ * rt_adaptive_add: after a reopen the active tiles carry different n_t.  Every active tile receives
+ * min(count, limit - n_t) further frame buffers, its next ones; a tile already at the limit receives none and
+ * stays active.  count < 1 or limit < 1 is RT_ERR_ARG, and so is, before anything is rendered, a tile that
+ * would pass 32 768 frame buffers.  The tiles that receive something are grouped by n_t, the groups taken in
+ * ascending n_t; each group is one rt_adapt_add of old over that group alone: the tile launch (at most
+ * chunk_fbs frame buffers each) from fb_first + n_t, then the fold over the group's list.  While nothing
+ * has been reopened there is one group and the launches are rt_adapt_add's.  counters (may be NULL) receives
+ * the call's totals, zero when no tile receives anything.  fbs stays max n_t.
+ *
+ * rt_adaptive_active: flags[tiles_x x tiles_y], 1 = active.
+ *
+ * Checkpoint blob (little-endian): the accumulator blob's 96-byte header with magic "RTADAPT1", version 1
+ * and fb_count = max n_t; then i32 n_t[tiles]; u8 active[tiles]; zero bytes up to an 8-byte offset;
+ * n_values float sums; zero bytes up to an 8-byte offset; n_values u64 S2; n_values u32 S1.  The header's
+ * payload hash is FNV-1a over everything after the header.  A valid blob: a header rt_accum_blob_info would
+ * accept, n_values and the size matching the tiling's tile grid, 0 <= n_t <= fb_count <= 32768 with some
+ * tile at fb_count, flags 0 or 1, every retired tile with n_t >= 2 (so fb_count = 0 means every tile active
+ * at 0), zero padding, a matching hash.  Save follows the size-query convention of rt_accum_save.  Load:
+ * RT_ERR_ARG for anything but a valid blob, with nothing allocated; RT_ERR_STATE when the context's scene
+ * differs from the blob's; chunk_fbs need not be the saved draw's.  A loaded accumulator continues
+ * byte-identically to one that never stopped: image, counts, noise map and every integer of the reports. */
+int rt_adaptive_add(rt_adapt* ad, int32_t count, int32_t limit, rt_counters* counters);
+int rt_adaptive_retire(rt_adapt* ad, float threshold, int32_t max_above, int32_t dilate, rt_adapt_report* rep);
+int rt_adaptive_reopen(rt_adapt* ad, float threshold, int32_t max_above, int32_t dilate, rt_adapt_report* rep);
+int rt_adaptive_active(rt_adapt* ad, uint8_t* flags);
+int rt_adaptive_save(rt_adapt* ad, void* blob, size_t cap, size_t* need);
+int rt_adaptive_load(rt_ctx* ctx, const void* blob, size_t n, int32_t chunk_fbs, rt_adapt** out);
+/* Host only (no context, no GPU; csrc/rt_adapt_blob.cpp): validate a checkpoint and fill info (RT_ERR_ARG
+ * for every violation listed above); its n_t and active flags (either may be NULL); its 8-bit image
+ * quant(sum / n_t) in rt_resolve's layout (RT_ERR_STATE with fb_count = 0); the measure as the device does
+ * it, each pixel at its tile's n_t (every output may be NULL, map is [owned_rows][width]; RT_ERR_STATE
+ * unless every n_t >= 2); build a blob from an info (fb_count = max n_t) and its arrays. */
+int rt_adaptive_blob_info(const void* blob, size_t n, rt_accum_info* info);
+int rt_adaptive_blob_tiles(const void* blob, size_t n, int32_t* tile_fbs, uint8_t* active);
+int rt_adaptive_blob_image(const void* blob, size_t n, uint8_t* out);
+int rt_adaptive_blob_measure(const void* blob, size_t n, float threshold, rt_adapt_report* rep, float* tile_max,
+                             int32_t* tile_above, float* map);
+int rt_adaptive_blob_pack(const rt_accum_info* info, const int32_t* tile_fbs, const uint8_t* active, const float* sums,
+                          const uint32_t* s1, const uint64_t* s2, void* blob, size_t cap, size_t* need);
 
 /* ------------------------------------------------------------------ host scene library */
 /* Builds one of the reference scenes (scenes.h) on the host: "basic", "first", "big1" (alias

@@ -12,9 +12,9 @@ Host mirror of the reference's interface for that path (names and argument meani
     previews, stop and resume through ``Context.accumulator`` / ``Accumulator`` / ``read_checkpoint``;
     ``until_noise=`` stops the draw once the per-pixel noise estimate of ``Accumulator.noise_monitor``
     (``NoiseMonitor``, ``read_noise``) says the 8-bit image has converged
-  * ``draw_adaptive(scene, settings, every=..., until_noise=...)`` — the same draw rendering only the
-    16 x 16 tiles that are still noisy (``Context.adaptive`` / ``AdaptiveAccumulator``,
-    ``Context.render_tiles``)
+  * ``draw_adaptive(scene, settings, every=..., until_noise=..., checkpoint=...)`` — the same draw
+    rendering only the 16 x 16 tiles that are still noisy (``Context.adaptive`` / ``AdaptiveAccumulator``,
+    ``Context.render_tiles``); it can be stopped, resumed and refined (``read_adaptive_checkpoint``)
   * ``Context.render_init / render / resolve`` — the kernels render_init (render.h:84-92) and
     render (render.h:94-113) behind the C ABI of include/rt_hip.h
 
@@ -228,6 +228,18 @@ ABI = {
     "rt_adapt_last_add_ms": (c_float, [c_void_p]),
     "rt_adapt_last_retire_ms": (c_float, [c_void_p]),
     "rt_adapt_destroy": (c_int, [c_void_p]),
+    "rt_adaptive_add": (c_int, [c_void_p, c_int32, c_int32, POINTER(rt_counters)]),
+    "rt_adaptive_retire": (c_int, [c_void_p, c_float, c_int32, c_int32, POINTER(rt_adapt_report)]),
+    "rt_adaptive_reopen": (c_int, [c_void_p, c_float, c_int32, c_int32, POINTER(rt_adapt_report)]),
+    "rt_adaptive_active": (c_int, [c_void_p, c_void_p]),
+    "rt_adaptive_save": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]),
+    "rt_adaptive_load": (c_int, [c_void_p, c_void_p, c_size_t, c_int32, POINTER(c_void_p)]),
+    "rt_adaptive_blob_info": (c_int, [c_void_p, c_size_t, POINTER(rt_accum_info)]),
+    "rt_adaptive_blob_tiles": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
+    "rt_adaptive_blob_image": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "rt_adaptive_blob_measure": (c_int, [c_void_p, c_size_t, c_float, POINTER(rt_adapt_report), c_void_p, c_void_p, c_void_p]),
+    "rt_adaptive_blob_pack": (c_int, [POINTER(rt_accum_info), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_size_t, POINTER(c_size_t)]),
     "rt_scene_build": (c_int, [c_char_p, POINTER(c_void_p)]),
     "rt_scene_build_ex": (c_int, [c_char_p, c_void_p, POINTER(c_void_p)]),
     "rt_obj_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
@@ -727,8 +739,9 @@ class NoiseMonitor:
 class AdaptiveAccumulator:
     """rt_adapt of include/rt_hip.h: a progressive draw that renders only the 16 x 16 tiles that are
     still noisy.  add() renders and folds in frame buffers for the active tiles, retire() stops every
-    active tile with at most max_above pixels above the threshold, for good.  Tile t of image() is
-    byte-identical to draw() with no_fb = counts()[t]."""
+    active tile with at most max_above pixels above the threshold (and, with dilate, no failing active
+    tile nearby), reopen() makes failing tiles active again.  Tile t of image() is byte-identical to draw()
+    with no_fb = counts()[t]; save() / load() continue bit-identically in another process."""
 
     def __init__(self, ctx: Context, handle: c_void_p, args: rt_render_args):
         import weakref
@@ -740,18 +753,69 @@ class AdaptiveAccumulator:
             ctx._accums = weakref.WeakSet()
         ctx._accums.add(self)
 
-    def add(self, count: int = 1) -> dict:
-        """Render the next count frame buffers for the active tiles and fold them in; this call's counters."""
+    @classmethod
+    def load(cls, ctx: Context, path: str, chunk_fbs: int = 1) -> "AdaptiveAccumulator":
+        """Continue from a checkpoint file (chunk_fbs need not be the saved draw's); RtError with status
+        RT_ERR_STATE when the context's scene is not the checkpoint's, RT_ERR_ARG for a malformed file."""
+        with open(path, "rb") as f:
+            blob = f.read()
+        return cls.from_blob(ctx, blob, chunk_fbs)
+
+    @classmethod
+    def from_blob(cls, ctx: Context, blob: bytes, chunk_fbs: int = 1) -> "AdaptiveAccumulator":
+        """load() from the bytes blob() returned."""
+        h = c_void_p()
+        ctx._check(lib().rt_adaptive_load(ctx._c, blob, len(blob), chunk_fbs, ctypes.byref(h)), "rt_adaptive_load")
+        i = rt_accum_info()
+        lib().rt_adaptive_blob_info(blob, len(blob), ctypes.byref(i))
+        return cls(ctx, h, i.args)
+
+    def add(self, count: int = 1, limit: int | None = None) -> dict:
+        """Render the next count frame buffers of every active tile and fold them in, no tile beyond limit
+        frame buffers (a tile at the limit receives nothing and stays active); this call's counters."""
         self.ctx._after_torch()
         cnt = rt_counters()
-        self.ctx._check(lib().rt_adapt_add(self._h, count, ctypes.byref(cnt)), "rt_adapt_add")
+        if limit is None:
+            self.ctx._check(lib().rt_adapt_add(self._h, count, ctypes.byref(cnt)), "rt_adapt_add")
+        else:
+            self.ctx._check(lib().rt_adaptive_add(self._h, count, limit, ctypes.byref(cnt)), "rt_adaptive_add")
         return cnt.as_dict()
 
-    def retire(self, threshold: float, max_above: int = 0) -> dict:
-        """Retire the active tiles with at most max_above pixels of noise > threshold; the report after."""
+    def retire(self, threshold: float, max_above: int = 0, dilate: int = 0) -> dict:
+        """Retire the active tiles with at most max_above pixels of noise > threshold, except those within
+        dilate tiles (Chebyshev, over the tile grid) of an active tile that fails; the report after."""
         rep = rt_adapt_report()
-        self.ctx._check(lib().rt_adapt_retire(self._h, threshold, max_above, ctypes.byref(rep)), "rt_adapt_retire")
+        self.ctx._check(lib().rt_adaptive_retire(self._h, threshold, max_above, dilate, ctypes.byref(rep)),
+                        "rt_adaptive_retire")
         return rep.as_dict()
+
+    def reopen(self, threshold: float, max_above: int = 0, dilate: int = 0) -> dict:
+        """Make every tile with more than max_above pixels of noise > threshold, and the tiles within dilate
+        of one, active again; none retires.  A reopened tile continues from its own count.  The report after."""
+        rep = rt_adapt_report()
+        self.ctx._check(lib().rt_adaptive_reopen(self._h, threshold, max_above, dilate, ctypes.byref(rep)),
+                        "rt_adaptive_reopen")
+        return rep.as_dict()
+
+    def active(self) -> np.ndarray:
+        """(tiles_y, tiles_x) bool: the tiles still rendered."""
+        out = np.zeros(((self._rows + 15) // 16, (self._width + 15) // 16), np.uint8)
+        self.ctx._check(lib().rt_adaptive_active(self._h, out.ctypes.data), "rt_adaptive_active")
+        return out.astype(bool)
+
+    def blob(self) -> bytes:
+        need = c_size_t()
+        self.ctx._check(lib().rt_adaptive_save(self._h, None, 0, ctypes.byref(need)), "rt_adaptive_save")
+        buf = ctypes.create_string_buffer(need.value)
+        self.ctx._check(lib().rt_adaptive_save(self._h, buf, need.value, None), "rt_adaptive_save")
+        return buf.raw
+
+    def save(self, path: str) -> None:
+        """Write the checkpoint to path: to a temporary name beside it first, then renamed over it."""
+        tmp = f"{path}.tmp{os.getpid()}"
+        with open(tmp, "wb") as f:
+            f.write(self.blob())
+        os.replace(tmp, path)
 
     def report(self, threshold: float) -> dict:
         """retire()'s report without retiring anything."""
@@ -836,6 +900,40 @@ def read_checkpoint(path: str) -> tuple[dict, np.ndarray]:
     if rc != 0:
         raise RtError(f"rt_accum_blob_image({path!r}) failed ({rc})", rc)
     return d, img
+
+
+def read_adaptive_checkpoint(path: str, threshold: float | None = None) -> tuple:
+    """(info, image, counts, active) of an adaptive checkpoint file and, with a threshold, (..., report,
+    noise map) too, by the host-only rt_adaptive_blob_* functions (no context, no GPU).  info as
+    Accumulator.info() with fb_count = the largest count; image (owned_rows, width, 3) uint8 with owned rows
+    ascending (None before the first frame buffer); counts int32 and active bool, (tiles_y, tiles_x)."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    i = rt_accum_info()
+    rc = lib().rt_adaptive_blob_info(blob, len(blob), ctypes.byref(i))
+    if rc != 0:
+        raise RtError(f"rt_adaptive_blob_info({path!r}) failed ({rc})", rc)
+    d = i.as_dict()
+    rows, width = d["n_values"] // (3 * d["width"]), d["width"]
+    ty, tx = (rows + 15) // 16, (width + 15) // 16
+    counts, active = np.zeros((ty, tx), np.int32), np.zeros((ty, tx), np.uint8)
+    rc = lib().rt_adaptive_blob_tiles(blob, len(blob), counts.ctypes.data, active.ctypes.data)
+    if rc != 0:
+        raise RtError(f"rt_adaptive_blob_tiles({path!r}) failed ({rc})", rc)
+    img = None
+    if d["fb_count"] > 0:
+        img = np.zeros((rows, width, 3), np.uint8)
+        rc = lib().rt_adaptive_blob_image(blob, len(blob), img.ctypes.data)
+        if rc != 0:
+            raise RtError(f"rt_adaptive_blob_image({path!r}) failed ({rc})", rc)
+    if threshold is None:
+        return d, img, counts, active.astype(bool)
+    rep = rt_adapt_report()
+    nmap = np.zeros((rows, width), np.float32)
+    rc = lib().rt_adaptive_blob_measure(blob, len(blob), threshold, ctypes.byref(rep), None, None, nmap.ctypes.data)
+    if rc != 0:
+        raise RtError(f"rt_adaptive_blob_measure({path!r}) failed ({rc})", rc)
+    return d, img, counts, active.astype(bool), rep.as_dict(), nmap
 
 
 def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context | None = None, every: int = 1,
@@ -923,16 +1021,25 @@ def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context 
 
 def draw_adaptive(curr_scene: Scene, settings: render_settings, ctx: Context | None = None, every: int = 1,
                   until_noise: float = 0.5, max_above: int = 0, min_fbs: int = 4, on_image=None, on_step=None,
-                  cam_mode: int = RT_CAM_REF_SLOT0, seed: int = 1984,
-                  chunk_fbs: int | None = None) -> tuple[np.ndarray, dict, np.ndarray]:
+                  cam_mode: int = RT_CAM_REF_SLOT0, seed: int = 1984, chunk_fbs: int | None = None,
+                  checkpoint: str | None = None, dilate: int = 0,
+                  reopen: bool = False) -> tuple[np.ndarray, dict, np.ndarray]:
     """draw() that stops rendering a 16 x 16 tile once at most max_above of its pixels have a noise
     estimate above until_noise (8-bit output levels; NoiseMonitor's definition), and goes on with the
-    others.  Each step adds `every` frame buffers to the active tiles; from max(2, min_fbs) frame buffers
-    on it then retires tiles and calls on_step(report, done); on_image(image, done) gets the PNG-order
-    image after every step.  Ends when no tile is active or settings.no_fb is reached.  Returns (image,
-    counters of everything rendered, counts): tile t of the image is byte-identical to draw() with no_fb
-    = counts[t].  Stopping a tile on its own samples' spread biases it slightly towards stopping while it
-    happens to look smooth; min_fbs is the only guard."""
+    others.  Each step adds `every` frame buffers to the active tiles, none beyond settings.no_fb; from
+    max(2, min_fbs) frame buffers on it then retires tiles and calls on_step(report, done); on_image(image,
+    done) gets the PNG-order image after every step.  Ends when no tile is active or every active tile is at
+    settings.no_fb.  Returns (image, counters of everything rendered by this call, counts): tile t of the
+    image is byte-identical to draw() with no_fb = counts[t].  Stopping a tile on its own samples' spread
+    biases it slightly towards stopping while it happens to look smooth; min_fbs guards against that, and
+    dilate = r keeps the passing tiles within r tiles of a failing one active too.
+
+    With a checkpoint path the state is saved there after every step (temporary name, then rename).  An
+    existing checkpoint of the same scene and settings is continued, byte-identically to a draw that never
+    stopped; one of another scene, of other settings or with more frame buffers than settings.no_fb raises
+    RtError.  reopen=True on a resumed draw first makes the tiles that fail until_noise / max_above (and
+    their neighbours within dilate) active again, each from its own count: a finished draw refined to a
+    tighter threshold."""
     if settings.image_height <= 0:
         settings.aspect_ratio = curr_scene.aspect
         settings.calc_all()
@@ -947,22 +1054,39 @@ def draw_adaptive(curr_scene: Scene, settings: render_settings, ctx: Context | N
         ctx.upload(curr_scene)
         args = make_args(settings.image_width, settings.image_height, settings.samples_per_pixel_per_fb,
                          0, 1, settings.max_depth, cam_mode, seed=seed)
-        ad = ctx.adaptive(args, chunk_fbs or every)
+        done, active = 0, True
+        if checkpoint and os.path.exists(checkpoint):
+            ad = AdaptiveAccumulator.load(ctx, checkpoint, chunk_fbs or every)
+            got, want = read_adaptive_checkpoint(checkpoint)[0], rt_accum_info(args, 0, 0).as_dict()
+            differ = [k for k in want if k not in ("fb_count", "n_values", "scene_fp") and got[k] != want[k]]
+            if differ or got["fb_count"] > settings.no_fb:
+                raise RtError(f"checkpoint {checkpoint!r} is of another draw: {differ or 'more frame buffers'}")
+            done = got["fb_count"]
+            if reopen and done >= 2:
+                ad.reopen(until_noise, max_above, dilate)
+            act = ad.active()
+            active = bool((act & (ad.counts() < settings.no_fb)).any())
+        else:
+            ad = ctx.adaptive(args, chunk_fbs or every)
         total = rt_counters().as_dict()
-        done, active, img = 0, True, None
-        while done < settings.no_fb and active:
-            n = min(every, settings.no_fb - done)
-            cnt = ad.add(n)
-            done += n
+        img = None
+        while active:
+            cnt = ad.add(every, limit=settings.no_fb)
+            counts = ad.counts()
+            done = int(counts.max())
             total = {k: total[k] + cnt[k] for k in total}
+            act = ad.active()
             if done >= max(2, min_fbs):
-                report = ad.retire(until_noise, max_above)
-                active = report["tiles_active"] > 0
-                if on_step is not None:
-                    on_step(report, done)
+                report = ad.retire(until_noise, max_above, dilate)
+                act = ad.active()
+            active = bool((act & (counts < settings.no_fb)).any())
+            if checkpoint:
+                ad.save(checkpoint)
+            if done >= max(2, min_fbs) and on_step is not None:
+                on_step(report, done)
             if on_image is not None:
                 on_image(ad.image(png_order=True), done)
-        if ad is not None and done:
+        if done:
             img = ad.image(png_order=True)
         return img, total, ad.counts()
     finally:

@@ -137,14 +137,6 @@ namespace {
 const char kMagic[8] = {'R', 'T', 'A', 'C', 'C', 'U', 'M', '1'};
 constexpr uint32_t kVersion = 1;
 
-// write_frame_buffer's quantisation (color.h:40-44) as the device code has it; NaN defined as 0.
-int quant(float x) {
-  const float r = std::sqrt(x);
-  if (!(r == r)) return 0;
-  const float c = r < 0.0f ? 0.0f : (r > 0.999f ? 0.999f : r);
-  return (int)(256.0f * c);
-}
-
 }  // namespace
 
 extern "C" {
@@ -186,7 +178,7 @@ int rt_accum_blob_image(const void* blob, size_t n, uint8_t* out) {
   for (int64_t k = 0; k < i.n_values; ++k) {
     float s;
     memcpy(&s, p + 4 * k, 4);
-    out[k] = (uint8_t)quant(s / nfb);
+    out[k] = (uint8_t)rtacc::host_quant(s / nfb);
   }
   return RT_OK;
 }

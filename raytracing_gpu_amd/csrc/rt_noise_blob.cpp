@@ -74,29 +74,16 @@ int rt_noise_blob_measure(const void* blob, size_t n, float threshold, rt_noise_
   const unsigned char* p1 = p2 + (size_t)i.n_values * sizeof(uint64_t);
   if (tile_max) for (int64_t t = 0; t < tiles_x * tiles_y; ++t) tile_max[t] = 0.0f;
   if (tile_above) for (int64_t t = 0; t < tiles_x * tiles_y; ++t) tile_above[t] = 0;
-  // n <= 32768 = 2^15, c^2 <= 65025 < 2^16, c^4 < 2^32: n S2 <= 2^15 n c^4 < 2^62 and S1^2 <= (n c^2)^2 < 2^62
-  // per channel (both <= 4.6e18), their three-channel sum <= 1.4e19 < 2^64; each term n S2 - S1^2 >= 0
-  // by Cauchy-Schwarz
-  const uint64_t nfb = (uint64_t)i.args.fb_count;
-  const double dn = (double)i.args.fb_count, dn1 = (double)(i.args.fb_count - 1);
   float max_noise = 0.0f;
   int64_t above = 0;
   for (int64_t r = 0; r < rows; ++r)
     for (int64_t x = 0; x < width; ++x) {
       const int64_t px = r * width + x;
-      uint64_t D = 0, S = 0;
-      for (int j = 0; j < 3; ++j) {
-        uint64_t s2;
-        uint32_t s1;
-        memcpy(&s2, p2 + 8 * (3 * px + j), 8);
-        memcpy(&s1, p1 + 4 * (3 * px + j), 4);
-        D += nfb * s2 - (uint64_t)s1 * s1;
-        S += s1;
-      }
-      const double a = (double)D / (3.0 * dn * dn * dn1 * 4228250625.0);
-      double m = (double)S / (3.0 * dn * 65025.0);
-      if (m < 0x1p-16) m = 0x1p-16;
-      const float noise = (float)(128.0 * std::sqrt(a / m));
+      uint64_t s2[3];
+      uint32_t s1[3];
+      memcpy(s2, p2 + 8 * 3 * px, sizeof(s2));
+      memcpy(s1, p1 + 4 * 3 * px, sizeof(s1));
+      const float noise = rtacc::host_pixel_noise(s1, s2, i.args.fb_count);  // the formula and its bound: rt_accum_blob.h
       if (map) map[px] = noise;
       const int64_t t = (r / rtacc::kNoiseTile) * tiles_x + x / rtacc::kNoiseTile;
       if (noise > max_noise) max_noise = noise;

@@ -932,6 +932,7 @@ int rt_noise_load(rt_accum* acc, const void* blob, size_t n, rt_noise** out) {
 // rt_render over a set of the noise monitor's tiles (16 x 16 pixels over (owned-row index, column)), and
 // the accumulator that stops rendering a tile once its own noise estimate is low enough (include/rt_hip.h).
 struct RT_INTERNAL rt_adapt : AccumCore {
+  uint64_t scene_fp = 0;
   Moments m;
   DevBuf<uint32_t> perm;              // [chunk x owned pixels] item list of a tile launch, allocated with scratch
   DevBuf<uint4> ntile;                // [tiles] the active noise tiles' list (tile_items_kernel's records)
@@ -940,7 +941,8 @@ struct RT_INTERNAL rt_adapt : AccumCore {
   std::vector<int32_t> active;        // ids of the active tiles, ascending
   std::vector<rttile::Rec> ntile_host;  // what ntile holds (kept alive for its upload)
   std::vector<float> h_max;           // host copies of the measure outputs; once have_measure, the retired
-  std::vector<int32_t> h_above;       // tiles' entries are current at threshold `measured` (theirs never change)
+  std::vector<int32_t> h_above;       // tiles' entries are current at threshold `measured` (theirs change only
+                                      // once a reopen, which measures every tile, has made them active again)
   float measured = 0.0f;
   bool have_measure = false;
   Timer retire_timer;  // around the last retire's measure kernel
@@ -983,6 +985,30 @@ int adapt_measure(rt_adapt* ad, float threshold, bool all, float* map_dev, bool 
   ad->measured = threshold;
   ad->have_measure = true;
   return RT_OK;
+}
+
+// The tiles within Chebyshev distance r >= 0 of a listed tile, over the tile grid (owned-row index, column):
+// flags[id] = 1.  A box is a row interval of column intervals: two passes of prefix counts, O(tiles).
+std::vector<uint8_t> dilated(const TileGrid& g, const std::vector<int32_t>& listed, int r) {
+  const int tx = g.tiles_x, ty = g.tiles_y;
+  std::vector<uint8_t> f((size_t)g.count(), 0), h(f.size(), 0), out(f.size(), 0);
+  for (int32_t t : listed) f[(size_t)t] = 1;
+  std::vector<int32_t> pre((size_t)std::max(tx, ty) + 1, 0);
+  for (int y = 0; y < ty; ++y) {  // h: a listed tile within r columns in the same row
+    for (int x = 0; x < tx; ++x) pre[(size_t)x + 1] = pre[(size_t)x] + f[(size_t)y * tx + x];
+    for (int x = 0; x < tx; ++x) {
+      const int lo = x - std::min(r, x), hi = (int)std::min<long long>(tx - 1, (long long)x + r);
+      h[(size_t)y * tx + x] = pre[(size_t)hi + 1] - pre[(size_t)lo] > 0;
+    }
+  }
+  for (int x = 0; x < tx; ++x) {  // out: an h within r rows in the same column
+    for (int y = 0; y < ty; ++y) pre[(size_t)y + 1] = pre[(size_t)y] + h[(size_t)y * tx + x];
+    for (int y = 0; y < ty; ++y) {
+      const int lo = y - std::min(r, y), hi = (int)std::min<long long>(ty - 1, (long long)y + r);
+      out[(size_t)y * tx + x] = pre[(size_t)hi + 1] - pre[(size_t)lo] > 0;
+    }
+  }
+  return out;
 }
 
 void adapt_report(const rt_adapt* ad, float threshold, rt_adapt_report* rep) {
@@ -1081,6 +1107,7 @@ int rt_adapt_create(rt_ctx* c, const rt_render_args* a, int32_t chunk_fbs, rt_ad
   HIPCHK(c, hipSetDevice(v.device));
   std::unique_ptr<rt_adapt> ad(new rt_adapt);
   core_init(*ad, c, a, chunk_fbs, rows);
+  ad->scene_fp = v.scene_fp;
   const size_t tiles = (size_t)g.count();
   ad->n_t.assign(tiles, 0);
   ad->h_max.assign(tiles, 0.0f);
@@ -1096,20 +1123,34 @@ int rt_adapt_create(rt_ctx* c, const rt_render_args* a, int32_t chunk_fbs, rt_ad
   return RT_OK;
 }
 
-int rt_adapt_add(rt_adapt* ad, int32_t count, rt_counters* counters) {
+int rt_adaptive_add(rt_adapt* ad, int32_t count, int32_t limit, rt_counters* counters) {
   if (!ad) return RT_ERR_ARG;
   rt_ctx* c = ad->ctx;
   const rt_render_args& a = ad->args;
-  int rc = add_check(*ad, count, rtacc::kNoiseMaxFbs - a.fb_count);
-  if (rc) return rc;
+  if (count < 1) return fail(c, RT_ERR_ARG, "count < 1");
+  if (limit < 1) return fail(c, RT_ERR_ARG, "limit < 1");
+  // the tiles that receive something, grouped by n_t (what a tile receives is a function of its n_t), the
+  // groups in ascending n_t, a group's tiles in ascending id; checked before anything is rendered
+  std::vector<std::pair<int32_t, int32_t>> by_n;  // (n_t, id)
+  for (int32_t t : ad->active) {
+    const int32_t n = ad->n_t[(size_t)t];
+    if (n >= limit) continue;  // at the limit: receives nothing, stays active
+    const int32_t give = std::min(count, limit - n);
+    if (give > rtacc::kNoiseMaxFbs - n) return fail(c, RT_ERR_ARG, "noise monitor: more than 32768 frame buffers");
+    if (a.fb_first > INT32_MAX - n - give) return fail(c, RT_ERR_ARG, "fb range overflows");
+    by_n.emplace_back(n, t);
+  }
+  if (ad->scene_gen != view(c).scene_gen) return fail(c, RT_ERR_STATE, "scene uploaded again since the accumulator was created");
   rt_counters total = {};
-  if (ad->active.empty()) {  // every tile has retired: nothing is rendered
+  if (by_n.empty()) {  // every tile has retired or is at the limit: nothing is rendered
     if (counters) *counters = total;
     return RT_OK;
   }
+  std::sort(by_n.begin(), by_n.end());
   const hipStream_t stream = stream_of(c);
   HIPCHK(c, hipSetDevice(view(c).device));
-  if ((rc = ensure_states(c, a.width, a.height, a.seed))) return rc;
+  int rc = ensure_states(c, a.width, a.height, a.seed);
+  if (rc) return rc;
   const TileGrid& g = ad->m.grid;
   if (!ad->scratch) {
     const size_t px = (size_t)ad->chunk * g.pixels();
@@ -1117,32 +1158,51 @@ int rt_adapt_add(rt_adapt* ad, int32_t count, rt_counters* counters) {
     if (!scratch.alloc(px * 3) || !ad->perm.alloc(px)) return fail(c, RT_ERR_NOMEM, "hipMalloc adaptive frame buffers");
     ad->scratch = std::move(scratch);
   }
-  rc = add_chunks(*ad, count, total, [&](const rt_render_args& r, int32_t n, rt_counters* cnt) {
-    TileLaunch tl{ad->perm.get(), rttile::records(ad->active.data(), (int)ad->active.size(), g.tiles_x, g.rows, g.width, n,
-                                                  ad->ntile_host)};
-    int e = tile_items(c, ad->ntile_host, g, n, ad->ntile.get(), ad->perm.get());
-    if (!e) e = render_dev(c, &r, ad->scratch.get(), cnt, &tl);
-    if (e) return e;
-    HIPCHK(c, ad->add_timer.start(stream));
-    hipLaunchKernelGGL(adapt_fold_kernel, dim3((unsigned)ad->active.size()), dim3(256), 0, stream, ad->ntile.get(), g.tiles_x,
-                       g.rows, g.width, ad->scratch.get(), ad->per_fb, n, ad->sums.get(), ad->m.s1.get(), ad->m.s2.get());
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, ad->add_timer.stop(stream));
-    ad->args.fb_count += n;
-    return (int)RT_OK;
-  });
-  if (rc) return rc;
-  for (int32_t t : ad->active) ad->n_t[(size_t)t] = a.fb_count;
+  std::vector<int32_t> group;
+  for (size_t k0 = 0; k0 < by_n.size();) {
+    const int32_t n0 = by_n[k0].first, give = std::min(count, limit - n0);
+    group.clear();
+    for (; k0 < by_n.size() && by_n[k0].first == n0; ++k0) group.push_back(by_n[k0].second);
+    // the group's frame buffers fb_first + n0 .., at most chunk per launch: the tile launch, then the fold
+    // over the same list, ordered on the stream before the next launch writes the scratch
+    for (int32_t done = 0; done < give;) {
+      const int32_t n = std::min(give - done, ad->chunk);
+      rt_render_args r = a;
+      r.fb_first = a.fb_first + n0 + done;
+      r.fb_count = n;
+      rt_counters cnt = {};
+      TileLaunch tl{ad->perm.get(), rttile::records(group.data(), (int)group.size(), g.tiles_x, g.rows, g.width, n, ad->ntile_host)};
+      rc = tile_items(c, ad->ntile_host, g, n, ad->ntile.get(), ad->perm.get());
+      if (!rc) rc = render_dev(c, &r, ad->scratch.get(), &cnt, &tl);
+      if (rc) return rc;
+      HIPCHK(c, ad->add_timer.start(stream));
+      hipLaunchKernelGGL(adapt_fold_kernel, dim3((unsigned)group.size()), dim3(256), 0, stream, ad->ntile.get(), g.tiles_x, g.rows,
+                         g.width, ad->scratch.get(), ad->per_fb, n, ad->sums.get(), ad->m.s1.get(), ad->m.s2.get());
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, ad->add_timer.stop(stream));
+      add_counters(total, cnt);
+      done += n;
+      for (int32_t t : group) ad->n_t[(size_t)t] = n0 + done;  // what the sums hold, also when a later launch fails
+      ad->args.fb_count = std::max(ad->args.fb_count, n0 + done);
+    }
+  }
   HIPCHK(c, hipMemcpyAsync(ad->tile_n.get(), ad->n_t.data(), ad->tile_n.bytes(), hipMemcpyHostToDevice, stream));
   HIPCHK(c, hipStreamSynchronize(stream));
   if (counters) *counters = total;
   return RT_OK;
 }
 
-int rt_adapt_retire(rt_adapt* ad, float threshold, int32_t max_above, rt_adapt_report* rep) {
+int rt_adapt_add(rt_adapt* ad, int32_t count, rt_counters* counters) {
+  if (!ad) return RT_ERR_ARG;
+  const int rc = add_check(*ad, count, rtacc::kNoiseMaxFbs - ad->args.fb_count);
+  return rc ? rc : rt_adaptive_add(ad, count, rtacc::kNoiseMaxFbs, counters);
+}
+
+int rt_adaptive_retire(rt_adapt* ad, float threshold, int32_t max_above, int32_t dilate, rt_adapt_report* rep) {
   if (!ad) return RT_ERR_ARG;
   rt_ctx* c = ad->ctx;
   if (max_above < 0) return fail(c, RT_ERR_ARG, "max_above < 0");
+  if (dilate < 0) return fail(c, RT_ERR_ARG, "dilate < 0");
   if (ad->args.fb_count < 2) return fail(c, RT_ERR_STATE, "noise needs at least 2 frame buffers");
   HIPCHK(c, hipSetDevice(view(c).device));
   // the active list on the device: the measure kernel reads the records' ids only
@@ -1152,11 +1212,120 @@ int rt_adapt_retire(rt_adapt* ad, float threshold, int32_t max_above, rt_adapt_r
                            stream_of(c)));
   const int rc = adapt_measure(ad, threshold, false, nullptr, true);
   if (rc) return rc;
-  std::vector<int32_t> keep;
+  std::vector<int32_t> keep;  // the failing active tiles
   for (int32_t t : ad->active)
     if (ad->h_above[(size_t)t] > max_above) keep.push_back(t);
-  ad->active.swap(keep);  // retiring is final: n_t of the others stays at fbs
+  if (dilate > 0) {  // ... and the active tiles within `dilate` of one
+    const std::vector<uint8_t> near = dilated(g, keep, dilate);
+    keep.clear();
+    for (int32_t t : ad->active)
+      if (near[(size_t)t]) keep.push_back(t);
+  }
+  ad->active.swap(keep);  // n_t of the others stays where it is
   if (rep) adapt_report(ad, threshold, rep);
+  return RT_OK;
+}
+
+int rt_adapt_retire(rt_adapt* ad, float threshold, int32_t max_above, rt_adapt_report* rep) {
+  return rt_adaptive_retire(ad, threshold, max_above, 0, rep);
+}
+
+int rt_adaptive_reopen(rt_adapt* ad, float threshold, int32_t max_above, int32_t dilate, rt_adapt_report* rep) {
+  if (!ad) return RT_ERR_ARG;
+  rt_ctx* c = ad->ctx;
+  if (max_above < 0) return fail(c, RT_ERR_ARG, "max_above < 0");
+  if (dilate < 0) return fail(c, RT_ERR_ARG, "dilate < 0");
+  if (ad->args.fb_count < 2) return fail(c, RT_ERR_STATE, "noise needs at least 2 frame buffers");
+  HIPCHK(c, hipSetDevice(view(c).device));
+  const int rc = adapt_measure(ad, threshold, true, nullptr, false);  // every tile, each at its own n_t
+  if (rc) return rc;
+  const TileGrid& g = ad->m.grid;
+  std::vector<int32_t> failing;
+  for (int32_t t = 0; t < (int32_t)g.count(); ++t)
+    if (ad->h_above[(size_t)t] > max_above) failing.push_back(t);
+  std::vector<uint8_t> on = dilated(g, failing, dilate);
+  for (int32_t t : ad->active) on[(size_t)t] = 1;  // never retires a tile
+  ad->active.clear();
+  for (int32_t t = 0; t < (int32_t)g.count(); ++t)
+    if (on[(size_t)t]) ad->active.push_back(t);
+  if (rep) adapt_report(ad, threshold, rep);
+  return RT_OK;
+}
+
+int rt_adaptive_active(rt_adapt* ad, uint8_t* flags) {
+  if (!ad) return RT_ERR_ARG;
+  if (!flags) return fail(ad->ctx, RT_ERR_ARG, "null flags");
+  std::fill(flags, flags + ad->n_t.size(), (uint8_t)0);
+  for (int32_t t : ad->active) flags[(size_t)t] = 1;
+  return RT_OK;
+}
+
+int rt_adaptive_save(rt_adapt* ad, void* blob, size_t cap, size_t* need) {
+  if (!ad) return RT_ERR_ARG;
+  rt_ctx* c = ad->ctx;
+  const size_t tiles = ad->n_t.size();
+  const rtacc::AdaptLayout l = rtacc::adapt_layout((size_t)ad->per_fb, tiles);
+  if (need) *need = l.total;
+  if (!blob && cap == 0) return RT_OK;  // size query
+  if (!blob || cap < l.total) return fail(c, RT_ERR_ARG, "checkpoint buffer too small");
+  const View v = view(c);
+  HIPCHK(c, hipSetDevice(v.device));
+  // every array lands in the blob's payload, then the header is packed around them
+  unsigned char* p = static_cast<unsigned char*>(blob);
+  memcpy(p + l.n_t, ad->n_t.data(), 4 * tiles);
+  rt_adaptive_active(ad, p + l.active);
+  const Moments& m = ad->m;
+  HIPCHK(c, hipMemcpyAsync(p + l.sums, ad->sums.get(), ad->sums.bytes(), hipMemcpyDeviceToHost, v.stream));
+  HIPCHK(c, hipMemcpyAsync(p + l.s2, m.s2.get(), m.s2.bytes(), hipMemcpyDeviceToHost, v.stream));
+  HIPCHK(c, hipMemcpyAsync(p + l.s1, m.s1.get(), m.s1.bytes(), hipMemcpyDeviceToHost, v.stream));
+  HIPCHK(c, hipStreamSynchronize(v.stream));
+  rt_accum_info info;
+  info.args = ad->args;
+  info.n_values = ad->per_fb;
+  info.scene_fp = ad->scene_fp;
+  if (rt_adaptive_blob_pack(&info, reinterpret_cast<const int32_t*>(p + l.n_t), p + l.active,
+                            reinterpret_cast<const float*>(p + l.sums), reinterpret_cast<const uint32_t*>(p + l.s1),
+                            reinterpret_cast<const uint64_t*>(p + l.s2), blob, cap, nullptr))
+    return fail(c, RT_ERR_ARG, "pack adaptive checkpoint");
+  return RT_OK;
+}
+
+int rt_adaptive_load(rt_ctx* c, const void* blob, size_t n, int32_t chunk_fbs, rt_adapt** out) {
+  if (!c) return RT_ERR_ARG;
+  if (!out) return fail(c, RT_ERR_ARG, "null adaptive accumulator pointer");
+  *out = nullptr;
+  rt_accum_info info;
+  if (rt_adaptive_blob_info(blob, n, &info)) return fail(c, RT_ERR_ARG, "malformed adaptive checkpoint");
+  const View v = view(c);
+  if (!v.have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
+  if (info.scene_fp != v.scene_fp) return fail(c, RT_ERR_STATE, "checkpoint belongs to another scene");
+  if (info.args.fb_first > INT32_MAX - info.args.fb_count) return fail(c, RT_ERR_ARG, "malformed adaptive checkpoint");
+  rt_adapt* ad = nullptr;
+  int rc = rt_adapt_create(c, &info.args, chunk_fbs, &ad);
+  if (rc) return rc;
+  const size_t tiles = ad->n_t.size();
+  const rtacc::AdaptLayout l = rtacc::adapt_layout((size_t)info.n_values, tiles);
+  if (ad->per_fb != info.n_values || l.total != n) rc = fail(c, RT_ERR_ARG, "malformed adaptive checkpoint");
+  const unsigned char* p = static_cast<const unsigned char*>(blob);
+  if (!rc) {
+    memcpy(ad->n_t.data(), p + l.n_t, 4 * tiles);
+    ad->active.clear();
+    for (size_t t = 0; t < tiles; ++t)
+      if (p[l.active + t]) ad->active.push_back((int32_t)t);
+    const Moments& m = ad->m;
+    if (hipMemcpyAsync(ad->sums.get(), p + l.sums, ad->sums.bytes(), hipMemcpyHostToDevice, v.stream) != hipSuccess ||
+        hipMemcpyAsync(m.s2.get(), p + l.s2, m.s2.bytes(), hipMemcpyHostToDevice, v.stream) != hipSuccess ||
+        hipMemcpyAsync(m.s1.get(), p + l.s1, m.s1.bytes(), hipMemcpyHostToDevice, v.stream) != hipSuccess ||
+        hipMemcpyAsync(ad->tile_n.get(), ad->n_t.data(), ad->tile_n.bytes(), hipMemcpyHostToDevice, v.stream) != hipSuccess ||
+        hipStreamSynchronize(v.stream) != hipSuccess)
+      rc = fail(c, RT_ERR_HIP, "copy adaptive checkpoint to device");
+  }
+  if (rc) {
+    rt_adapt_destroy(ad);
+    return rc;
+  }
+  ad->args.fb_count = info.args.fb_count;  // the first measure runs over every tile (have_measure is false)
+  *out = ad;
   return RT_OK;
 }
 
