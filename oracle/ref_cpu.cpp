@@ -232,6 +232,15 @@ static std::atomic<long long> g_cap_n{0};
 static long long g_cap_max = 0;
 static float* g_cap = nullptr;
 static thread_local bool tl_h20 = false;
+// Scene RNG state at the start of every build that draws (8 words: kind 0 = BVH build, 1 = perlin
+// tables; primitive count; d, v0..v4), in build order: the reference-header pins start from them.
+static thread_local std::vector<uint32_t> tl_marks;
+static thread_local bool tl_marking = false;  // only while a scene is being created
+static void mark_state(uint32_t kind, uint32_t n, const Rng& s) {
+  if (!tl_marking) return;
+  const uint32_t w[8] = {kind, n, s.d, s.v[0], s.v[1], s.v[2], s.v[3], s.v[4]};
+  tl_marks.insert(tl_marks.end(), w, w + 8);
+}
 
 static inline int rand_int(Draw& g, int lo, int hi) {  // common.h:49-52 (may return hi+1: H20)
   const int r = (int)g.u((float)lo, (float)(hi + 1));
@@ -291,6 +300,7 @@ struct Perlin {  // perlin.h:9-127
     }
   }
   explicit Perlin(Draw& g) {
+    mark_state(1, 0, *g.s);
     for (int i = 0; i < 256; ++i) ranvec[i] = unit(g.v3(-1.0f, 1.0f));
     perm(g, px);
     perm(g, py);
@@ -812,6 +822,7 @@ struct RefBvh : Hittable {
 
   RefBvh(const std::vector<const Hittable*>& in, float time0, float time1, Draw& g) : objs(in) {
     n = (int)objs.size();
+    mark_state(0, (uint32_t)n, *g.s);
     rows = 0;
     while ((1 << rows) < n) ++rows;
     if (n < 3) { fprintf(stderr, "RefBvh: n < 3 unsupported\n"); abort(); }
@@ -972,6 +983,8 @@ struct ref_scene {
   std::vector<std::unique_ptr<Texture>> ts;
   std::vector<float> table;  // big_scene1 object table, 13 floats per object
   std::vector<int> axes;
+  std::vector<uint32_t> marks;             // mark_state's records of the build
+  std::vector<const Hittable*> flat_prims; // ref_scene_from_flat: the primitives by index
   bool h20 = false;
 
   template <class T, class... A> T* H(A&&... a) { T* p = new T(std::forward<A>(a)...); hs.emplace_back(p); return p; }
@@ -1470,6 +1483,7 @@ struct FlatBuilder {
     cam.t1 = c.time1;
     s.background = V3(f.background[0], f.background[1], f.background[2]);
     s.aspect = f.aspect;
+    s.flat_prims = prim;
     return true;
   }
 };
@@ -1533,6 +1547,11 @@ int ref_scene_create_ex(const char* name, int rtl, const ref_assets* a, ref_scen
   Rng st = rng_init(1984, 0, 0);  // world_init  scenes.h:28-32
   Draw g{&st, rtl != 0};
   tl_h20 = false;
+  tl_marks.clear();
+  struct Marking {
+    Marking() { tl_marking = true; }
+    ~Marking() { tl_marking = false; }
+  } marking;
   const std::string n(name);
   if (n == "basic") build_basic(*s);
   else if (n == "first") build_first(*s);
@@ -1552,6 +1571,7 @@ int ref_scene_create_ex(const char* name, int rtl, const ref_assets* a, ref_scen
   else if (n == "coincident_step") build_coincident(*s, g, true);
   else return 1;
   s->h20 = tl_h20;
+  s->marks = tl_marks;
   *out = s.release();
   return 0;
 }
@@ -1589,6 +1609,44 @@ int ref_scene_table(const ref_scene* s, float* out, int max_rows) {
   const int rows = (int)s->table.size() / 13;
   if (out) memcpy(out, s->table.data(), sizeof(float) * 13 * std::min(rows, max_rows));
   return rows;
+}
+void ref_scene_camera(const ref_scene* s, float out[24]) {
+  const Camera& c = s->cam;
+  const V3* v[7] = {&c.origin, &c.llc, &c.horiz, &c.vert, &c.u, &c.v, &c.w};
+  for (int k = 0; k < 7; ++k) {
+    out[3 * k] = v[k]->x;
+    out[3 * k + 1] = v[k]->y;
+    out[3 * k + 2] = v[k]->z;
+  }
+  out[21] = c.lens;
+  out[22] = c.t0;
+  out[23] = c.t1;
+}
+int ref_scene_rng_marks(const ref_scene* s, uint32_t* out, int max_marks) {
+  const int n = (int)s->marks.size() / 8;
+  if (out) memcpy(out, s->marks.data(), sizeof(uint32_t) * 8 * std::min(n, max_marks));
+  return n;
+}
+int ref_bvh_build(const ref_scene* s, int first, int n, float t0, float t1, const uint32_t* state_in, int32_t* leaf_a,
+                  int32_t* leaf_b, float* lo, float* hi, int32_t* axes, uint32_t* state_out) {
+  if (!s || n < 3 || first < 0 || (size_t)first + n > s->flat_prims.size()) return 1;
+  Rng st{state_in[0], {state_in[1], state_in[2], state_in[3], state_in[4], state_in[5]}};
+  Draw g{&st, false};
+  const std::vector<const Hittable*> in(s->flat_prims.begin() + first, s->flat_prims.begin() + first + n);
+  const RefBvh b(in, t0, t1, g);
+  const int inner = (1 << b.rows) - 1;
+  for (int k = 0; k < inner; ++k) {
+    axes[k] = b.axes[k];
+    leaf_a[k] = b.leaf_a[k] < 0 ? -1 : first + b.leaf_a[k];
+    leaf_b[k] = b.leaf_b[k] < 0 ? -1 : first + b.leaf_b[k];
+    for (int a = 0; a < 3; ++a) {
+      lo[3 * k + a] = b.bounds[k].lo[a];
+      hi[3 * k + a] = b.bounds[k].hi[a];
+    }
+  }
+  const uint32_t w[6] = {st.d, st.v[0], st.v[1], st.v[2], st.v[3], st.v[4]};
+  memcpy(state_out, w, sizeof(w));
+  return 0;
 }
 int ref_scene_bvh_axes(const ref_scene* s, int* out, int max_n) {
   const int n = (int)s->axes.size();

@@ -49,6 +49,18 @@ void ref_scene_set_camera(ref_scene* s, const float from[3], const float at[3], 
 /* Object table of big_scene1, 13 floats per row: type, material, centre0[3], centre1[3], radius,
  * albedo[3], fuzz-or-ir. */
 int ref_scene_table(const ref_scene* s, float* out, int max_rows);
+/* The scene camera in rt_camera's layout (include/rt_hip.h): origin, lower_left, horizontal, vertical, u,
+ * v, w, then lens_radius, time0, time1. */
+void ref_scene_camera(const ref_scene* s, float out[24]);
+/* Scene RNG state at the start of every build that draws, in build order, 8 words each: kind (0 = a BVH
+ * build, bvh.h:270-346; 1 = perlin's tables, perlin.h:63-76), the BVH's primitive count, then d, v0..v4.
+ * Returns the number of records. */
+int ref_scene_rng_marks(const ref_scene* s, uint32_t* out, int max_marks);
+/* The oracle's BVH build over primitives [first, first + n) of a ref_scene_from_flat scene, from
+ * state_in: per inner node in heap order (2^ceil(log2 n) - 1) its box, its leaves' primitives (last row;
+ * -1 = none) and the axis drawn for it; the state afterwards.  n >= 3. */
+int ref_bvh_build(const ref_scene* s, int first, int n, float t0, float t1, const uint32_t* state_in, int32_t* leaf_a,
+                  int32_t* leaf_b, float* lo, float* hi, int32_t* axes, uint32_t* state_out);
 /* Sequence of BVH split axes drawn during the build (bvh.h:294), -1 padded. */
 int ref_scene_bvh_axes(const ref_scene* s, int* out, int max_n);
 

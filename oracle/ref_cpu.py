@@ -44,6 +44,9 @@ def lib() -> ctypes.CDLL:
         L.ref_scene_h20.argtypes = [c_void_p]
         L.ref_scene_table.argtypes = [c_void_p, c_void_p, c_int]
         L.ref_scene_bvh_axes.argtypes = [c_void_p, c_void_p, c_int]
+        L.ref_scene_camera.argtypes = [c_void_p, c_void_p]
+        L.ref_scene_rng_marks.argtypes = [c_void_p, c_void_p, c_int]
+        L.ref_bvh_build.argtypes = [c_void_p, c_int, c_int, c_float, c_float] + [c_void_p] * 7
         L.ref_scene_set_camera.argtypes = [c_void_p, POINTER(c_float), POINTER(c_float), c_float, c_float, c_float]
         L.ref_render.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_void_p, c_void_p, POINTER(ref_counters)]
@@ -126,6 +129,23 @@ class RefScene:
         n = lib().ref_scene_bvh_axes(self._h, a.ctypes.data, a.size)
         return a[:n].copy()
 
+    def camera(self) -> np.ndarray:
+        """The scene camera as rt_camera's 24 floats."""
+        out = np.zeros(24, np.float32)
+        lib().ref_scene_camera(self._h, out.ctypes.data)
+        return out
+
+    def rng_marks(self) -> list:
+        """(kind, n, state) of every build that drew from the scene RNG, in build order: kind 0 = a BVH
+        build over n primitives, 1 = perlin's tables; state = the six XORWOW words before it."""
+        m = np.zeros((256, 8), np.uint32)
+        n = lib().ref_scene_rng_marks(self._h, m.ctypes.data, 256)
+        return [(int(r[0]), int(r[1]), r[2:].copy()) for r in m[:n]]
+
+    def bvh_build(self, first: int, n: int, state, t0: float = 0.0, t1: float = 1.0) -> dict:
+        """The oracle's BVH build over primitives [first, first + n) of a from_flat scene."""
+        return bvh_build_call(lib().ref_bvh_build, self._h, first, n, state, t0, t1)
+
     def set_camera(self, frm, at, vfov, aperture, focus) -> None:
         f = (c_float * 3)(*frm)
         a = (c_float * 3)(*at)
@@ -152,6 +172,18 @@ class RefScene:
                 lib().ref_scene_destroy(self._h)
         except Exception:
             pass
+
+
+def bvh_build_call(fn, handle, first: int, n: int, state, t0: float, t1: float) -> dict:
+    """Calls a BVH build entry point (the oracle's or the reference headers': one signature)."""
+    inner = (1 << max(n - 1, 1).bit_length()) - 1
+    out = {"leaf_a": np.zeros(inner, np.int32), "leaf_b": np.zeros(inner, np.int32), "lo": np.zeros((inner, 3), np.float32),
+           "hi": np.zeros((inner, 3), np.float32), "axes": np.zeros(inner, np.int32), "state": np.zeros(6, np.uint32)}
+    st = np.ascontiguousarray(state, np.uint32)
+    rc = fn(handle, first, n, t0, t1, st.ctypes.data, *[out[k].ctypes.data for k in ("leaf_a", "leaf_b", "lo", "hi", "axes", "state")])
+    if rc != 0:
+        raise RuntimeError(f"BVH build failed ({rc})")
+    return out
 
 
 def quantize_fb(fb: np.ndarray, W: int, H: int) -> np.ndarray:

@@ -105,7 +105,8 @@ def build_oracle(force: bool = False) -> str:
     if force:
         subprocess.run(["make", "-C", odir, "clean"], check=True)
     subprocess.run(args, check=True, stdout=subprocess.DEVNULL)
-    # the reference's own vendored stb_image, compiled where it lies (test pin for image decoding)
+    # where the reference is present, compiled where it lies into oracle/_ref/: its vendored stb_image (test
+    # pin for image decoding) and its class headers as host C++ (oracle/refhdr/: test pin for the oracle)
     if os.path.exists("/root/reference/external/stb_image.h"):
         subprocess.run(["make", "-C", odir, "ref"], check=True, stdout=subprocess.DEVNULL)
     return os.path.join(odir, "_build", "libref_cpu.so")

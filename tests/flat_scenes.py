@@ -161,7 +161,8 @@ class FlatScene:
     def tri(self, a, b, c, mat, uv=(0, 0, 1, 0, 0, 1), normals=None) -> int:
         a, b, c = v3(a), v3(b), v3(c)
         e0, e1 = b - a, c - a
-        d00, d01, d11 = F32(e0 @ e0), F32(e0 @ e1), F32(e1 @ e1)
+        dot = lambda p, q: p[0] * q[0] + p[1] * q[1] + p[2] * q[2]  # triangle.h:28-30's order, every step in float32
+        d00, d01, d11 = dot(e0, e0), dot(e0, e1), dot(e1, e1)
         t = np.zeros((), TRI_DTYPE)
         t["v0"], t["v1"], t["v2"], t["e0"], t["e1"] = a, b, c, e0, e1
         t["d00"], t["d01"], t["d11"] = d00, d01, d11
