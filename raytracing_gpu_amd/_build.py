@@ -24,9 +24,12 @@ HIP_SOURCES = ["rt_kernels.hip", "rt_progressive.hip", "rt_scene.cpp", "rt_obj.c
 HIP_DEPS = HIP_SOURCES + sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
 # -ffp-contract=off: no FMA contraction anywhere, so every float op rounds like the reference's
 # C++ source and like the CPU oracle; fp32 div/sqrt correctly rounded (IEEE) on the device.
+# -fno-slp-vectorize: no v_pk_mul_f32 / v_pk_add_f32 from adjacent scalar float ops.  A packed f32 op
+# issues at half rate on gfx950, so it saves nothing per element, and its operand shuffles and hazard
+# s_nops cost registers and instructions; each lane's arithmetic is the same IEEE ops.
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-    "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math",
+    "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-fno-slp-vectorize",
 ]
 
 

@@ -949,13 +949,14 @@ __device__ __forceinline__ bool trav_step(const DScene& S, int fb, const Ray& r,
 // leaf_pass_min: 0 = the variant tests its leaves in the step that finds them (trav_step);
 // above 64 = the count never fires and the vote is one ballot per step (measured fastest on C2:
 // every counting threshold lost more to the second ballot than its fuller passes gained).
-// The triangle-mesh variants gain as well (C4 -2.6 % at 65, -3.2 % at 16) but spill two more VGPRs
-// at the 128 cap, so they keep the immediate pass.
+// The triangle-mesh variants defer as well (C4 -5 %): built without SLP packing they
+// hold the deferral in 123 VGPRs with nothing spilled (packed, it cost two more spilled VGPRs at the
+// 128 cap and was left off).
 #ifndef RT_LEAF_MIN
 #define RT_LEAF_MIN 65
 #endif
 #ifndef RT_LEAF_MIN_TRI
-#define RT_LEAF_MIN_TRI 0
+#define RT_LEAF_MIN_TRI 65
 #endif
 constexpr int leaf_pass_min(int F) {
   return (F & F_STEP) == 0 || (F & F_WORLD) != 0 ? 0 : ((F & F_TRI) != 0 ? RT_LEAF_MIN_TRI : RT_LEAF_MIN);
@@ -1009,34 +1010,27 @@ __device__ __forceinline__ void trav_leaf(const DScene& S, int ch, const Ray& r,
   RT_STAMP(3);
 }
 
-// Decision part: descend into the nearer hit child and push the other, else pop; false when the
-// search has ended.  hl / hr are the hit INNER children (hit leaves already cleared by the caller).
-template <int F>
-__device__ __forceinline__ bool trav_next(const DScene& S, bool hl, bool hr, float tl, float tr, int c0, int c1,
-                                          int& cur, int& sp, bool& overflow) {
-  stack_t<F>* stk = stack_of<F>(S);
-  constexpr int BS = render_block<F>();
-  if (hl && hr) {
-    const bool right_first = tr < tl;
-    if (sp < kStackDepth) stk[BS * sp++] = (stack_t<F>)(right_first ? c0 : c1);
-    else overflow = true;
-    cur = right_first ? c1 : c0;
-    return true;
-  }
-  if (hl || hr) {
-    cur = hl ? c0 : c1;
-    return true;
-  }
-  if (sp == 0) return false;
-  cur = stk[BS * --sp];
-  return true;
-}
-
 // Node part of a deferring step: the pair, the decision, and the hit leaf children in n0 / n1
 // (child words, 0: none) instead of their tests.
+// The decision (descend into the nearer hit inner child and push the other, else pop; false when the
+// search has ended) is trav_step's, written as selects so that the step is one straight line (as
+// nested branches it was six of the node part's scalar instructions, each waiting on the last):
+//  - the stack top is read with the pair's loads, before the box tests: its address needs sp only.
+//    At sp == 0 it reads entry 0, which nothing uses (pop is false there);
+//  - the far child is written by one store under the lanes' mask `push`.  The stacks fill their LDS
+//    exactly (kStackDepth entries per lane, no spare slot), so at sp == kStackDepth the store is
+//    masked off, never redirected, and `overflow` is set as in trav_step;
+//  - a step that does not push leaves every entry below sp as it was (it stores nothing); entries at
+//    sp and above are don't-care.
+// cur, sp, overflow, n0, n1 and the return value are trav_step's for every input (where the search
+// ends, cur keeps its value as there), so the visit order, the cut, the hit leaves handed to
+// leaf_vote, and with them every float operation and RNG draw, are unchanged.
 template <int F>
 __device__ __forceinline__ bool trav_node(const DScene& S, int fb, V oi, V finv, float tmin, float tmax, float bhi,
                                           int& cur, int& sp, bool& overflow, unsigned& nnode, int& n0, int& n1) {
+  stack_t<F>* stk = stack_of<F>(S);
+  constexpr int BS = render_block<F>();
+  const int popped = stk[BS * (sp > 0 ? sp - 1 : 0)];
   float tl, tr;
   bool hl, hr;
   int c0, c1;
@@ -1044,9 +1038,19 @@ __device__ __forceinline__ bool trav_node(const DScene& S, int fb, V oi, V finv,
   const bool la = hl && c0 < 0, lb = hr && c1 < 0;
   n0 = la ? c0 : (lb ? c1 : 0);
   n1 = (la && lb) ? c1 : 0;
-  if (la) hl = false;
-  if (lb) hr = false;
-  return trav_next<F>(S, hl, hr, tl, tr, c0, c1, cur, sp, overflow);
+  hl = hl && c0 >= 0;
+  hr = hr && c1 >= 0;
+  const bool both = hl && hr, any = hl || hr;
+  const bool right_first = tr < tl;
+  const int near = both ? (right_first ? c1 : c0) : (hl ? c0 : c1);
+  const int far = right_first ? c0 : c1;
+  const bool push = both && sp < kStackDepth;
+  const bool pop = !any && sp > 0;
+  overflow = overflow || (both && !push);
+  if (push) stk[BS * sp] = (stack_t<F>)far;
+  cur = any ? near : (pop ? popped : cur);
+  sp += (int)push - (int)pop;
+  return any || pop;
 }
 
 // The wave's vote after the node part (every lane of the wave, traversing or not; n0 = n1 = 0 for a
