@@ -1,6 +1,7 @@
 // rt_ctx_internal.h -- internal: what rt_progressive.hip (the accumulators, rt_render_tiles) uses of the
 // render side.  Everything here is defined in rt_kernels.hip; struct rt_ctx itself stays private to that
 // file.  Hidden visibility: the library exports what include/rt_hip.h declares and none of these.
+// The owned device buffers of both files (DevBuf, Staged) are rt_devbuf.h, over device_ptr below.
 #ifndef RT_CTX_INTERNAL_H
 #define RT_CTX_INTERNAL_H
 

@@ -173,7 +173,7 @@ __device__ __forceinline__ unsigned long long rt_realtime() {
   do {                                                                                                \
     if (const char* p_ = getenv("RT_ITEM_COST_OUT")) {                                                \
       std::vector<uint16_t> ic_((size_t)(items));                                                     \
-      HIPCHK(c, hipMemcpyAsync(ic_.data(), (c)->item_cost, ic_.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, \
+      HIPCHK(c, hipMemcpyAsync(ic_.data(), (c)->item_cost.get(), ic_.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, \
                                (c)->stream));                                                         \
       HIPCHK(c, hipStreamSynchronize((c)->stream));                                                   \
       if (FILE* f_ = fopen(p_, "wb")) {                                                               \
@@ -186,7 +186,7 @@ __device__ __forceinline__ unsigned long long rt_realtime() {
   do {                                                                                                \
     if (const char* p_ = getenv("RT_PROBE_OUT")) {                                                    \
       std::vector<uint16_t> pc_((size_t)(n));                                                         \
-      HIPCHK(c, hipMemcpyAsync(pc_.data(), (c)->probe_cost, pc_.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, \
+      HIPCHK(c, hipMemcpyAsync(pc_.data(), (c)->probe_cost.get(), pc_.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, \
                                (c)->stream));                                                         \
       HIPCHK(c, hipStreamSynchronize((c)->stream));                                                   \
       if (FILE* f_ = fopen(p_, "wb")) {                                                               \

@@ -39,6 +39,7 @@
 #include "rt_accum_blob.h"
 #include "rt_ctx_internal.h"
 #include "rt_detmath.h"
+#include "rt_devbuf.h"
 #include "rt_diag.h"
 #include "rt_host_geom.h"
 #include "rt_quant.h"
@@ -3118,42 +3119,59 @@ __global__ __launch_bounds__(kBlock) void bin_masks_kernel(const float4* __restr
 }  // namespace
 
 // ====================================================================== host side (C ABI)
-struct rt_ctx {
-  int device = 0;
-  rt_ctx_options opt{};  // rt_ctx_set_options (defaults: rt_ctx_options_default)
+// A cached configuration: the values a device table or a schedule was built from.  Invalid (all -1)
+// compares unequal to every real configuration (scene_gen >= 0 leads each one).
+template <int N>
+struct Key {
+  std::array<long long, N> v;
+  Key() { invalidate(); }
+  template <class... A>
+  Key(A... a) : v{{(long long)a...}} { static_assert(sizeof...(A) == N, "one value per component"); }
+  bool operator==(const Key& o) const { return v == o.v; }
+  bool operator!=(const Key& o) const { return v != o.v; }
+  void invalidate() { v.fill(-1); }
+};
+
+// The context's stream and events: a base of rt_ctx, so they are released after every member buffer.
+struct StreamOwner {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;  // render call start, its end; render kernel start
+  ~StreamOwner() {
+    for (hipEvent_t e : {ev0, ev1, ev2})
+      if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+struct rt_ctx : StreamOwner {
+  int device = 0;
+  rt_ctx_options opt{};  // rt_ctx_set_options (defaults: rt_ctx_options_default)
   std::string err;
   std::vector<void*> scene_bufs;
   DScene scene{};
   bool have_scene = false;
-  uint4* states = nullptr;
-  long long states_n = 0;
+  DevBuf<uint4> states;  // uint4 pairs
+  long long states_n = 0;  // the states in use (states_are): width * height of the last rt_render_init
   uint64_t states_seed = 0;
-  uint32_t* seq = nullptr;
-  uint32_t* jump_tab = nullptr;  // byte tables of the subsequence jumps (init_states_kernel)
-  unsigned long long* work = nullptr;  // [0] work counter, [1..4] counters
-  int32_t* row_map = nullptr;  // [rows] {owned row r, image row j} in processing order (RenderParams::row_q)
+  DevBuf<uint32_t> seq;
+  DevBuf<uint32_t> jump_tab;  // byte tables of the subsequence jumps (init_states_kernel)
+  DevBuf<unsigned long long> work;  // [0] work counter, [1..4] counters
+  DevBuf<int32_t> row_map;  // int32 pairs: [rows] {owned row r, image row j} in processing order (RenderParams::row_q)
   std::vector<int32_t> row_map_host;  // what row_map holds (uploaded only when it changes)
-  int row_cap = 0;
-  unsigned long long* row_cost = nullptr;  // device, per image row
-  int row_cost_cap = 0;
+  DevBuf<unsigned long long> row_cost;  // device, per image row
   // Per-row cost of the last launch of (scene generation, W, H, spp, depth): the schedule of the
   // next launch of that configuration (no pixel result depends on the order).
   std::vector<unsigned long long> host_cost;
-  long long cost_key[5] = {-1, -1, -1, -1, -1};
+  Key<5> cost_key;
   // Item schedule of the last configuration (scene generation, size, spp, depth, fb range, tiling):
   // per-item segment counts of its measuring launch -> longest items first (perm).
-  uint16_t* item_cost = nullptr;
-  uint16_t* probe_cost = nullptr;  // per (owned row, pixel): the probe launch's segment counts
-  long long probe_cap = 0;
-  uint32_t* spread_tmp = nullptr;  // probe_schedule: a copy of perm's head, gathered back spread
-  long long spread_cap = 0;
-  uint32_t* perm = nullptr;
-  long long item_cap = 0;
+  DevBuf<uint16_t> item_cost;
+  DevBuf<uint16_t> probe_cost;  // uint16 pairs, per (owned row, pixel): the probe launch's segment counts, raw then smoothed
+  DevBuf<uint32_t> spread_tmp;  // probe_schedule: a copy of perm's head, gathered back spread
+  DevBuf<uint32_t> perm;
   static constexpr int kKey = 11;
-  long long perm_key[kKey] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-  long long pending_key[kKey] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};  // measured, schedule not built yet
+  Key<kKey> perm_key;
+  Key<kKey> pending_key;  // measured, schedule not built yet
   unsigned long long pending_segs = 0;
   unsigned long long n_long = 0;
   // Split samples of the longest items (render_step_kernel; see rt_render): n_split perm positions,
@@ -3161,27 +3179,22 @@ struct rt_ctx {
   unsigned long long n_split = 0;
   int split_state = -1;
   uint64_t split_seed = 0;
-  uint4* ckpt = nullptr;
-  long long ckpt_cap = 0;  // uint4 pairs
-  float* contrib = nullptr;
-  long long contrib_cap = 0;  // floats
-  uint4* cam_st = nullptr;
-  long long cam_st_cap = 0;  // uint4 pairs
+  DevBuf<uint4> ckpt;  // uint4 pairs
+  DevBuf<float> contrib;  // float triples
+  DevBuf<uint4> cam_st;  // uint4 pairs
   // Claim order of the split launches (RenderParams::order), built on the first one after a
   // recording (order_scatter_kernel); rest_gt[v]: unsplit perm positions (from n_split on) whose
   // key -- cost bucket midpoint, clamped to 256 -- exceeds v; order_tab: the kernel's tables, its
   // histogram and cursors (order_tab_host: the host copy of the tables).
-  uint32_t* order = nullptr;
-  long long order_cap = 0;
+  DevBuf<uint32_t> order;
   bool order_ok = false;
   long long rest_n = -1;
   std::vector<unsigned> rest_gt;
-  unsigned* order_tab = nullptr;
+  DevBuf<unsigned> order_tab;
   std::vector<unsigned> order_tab_host;
   // scratch of the device sorts (sort_keys / sort_scatter): keys, then per-tile tables
-  uint8_t* sort_scratch = nullptr;
-  long long sort_scratch_cap = 0;
-  long long cam_st_key[3] = {-1, -1, -1};
+  DevBuf<uint8_t> sort_scratch;
+  Key<3> cam_st_key;
   long long scene_gen = 0;
   uint64_t scene_fp = 0;  // rtacc::scene_fingerprint of the uploaded scene (accumulator checkpoints)
   int cus = 0, blocks_per_cu[32] = {0};  // per kernel variant (kVariants)
@@ -3195,21 +3208,19 @@ struct rt_ctx {
   float last_kernel_ms = 0.0f;  // ... its render kernel (and split merge) alone
   int last_sched = 0;  // RT_SCHED_* of the last render launch
   char last_kernel[48] = "";  // rocprof name stem of the last render launch, e.g. render_step_kernel<25730>
-  float* dbg = nullptr;  // audit log: [0] = count, then 16 floats per entry
+  DevBuf<float> dbg;  // audit log: [0] = count, then 16 floats per entry
   // Camera-ray candidate lists (world = one BVH): bounding spheres of the world BVH's primitives
   // over the shutter (scene buffers) and the per-tile lists of the last (scene, W, H).
   const float4* bin_sph = nullptr;
   const int32_t* bin_ids = nullptr;
   int bin_n = 0;
   // REF camera mode: per-sample lens offset + time of the last (scene, seed, spp) (camera_table)
-  float4* cam_tab = nullptr;
-  long long cam_cap = 0;
-  long long cam_key[3] = {-1, -1, -1};
+  DevBuf<float4> cam_tab;
+  Key<3> cam_key;
   std::vector<float4> cam_host;  // stays alive while the upload is in flight
   std::vector<uint4> cam_st_host;
-  int32_t* tiles = nullptr;  // [ntiles] counts, then [ntiles * kTileCap] entries
-  long long tiles_cap = 0;
-  long long tiles_key[3] = {-1, -1, -1};
+  DevBuf<int32_t> tiles;  // [ntiles] masks, or [ntiles] counts, then [ntiles * kTileCap] entries
+  Key<3> tiles_key;
 };
 
 namespace {
@@ -3593,24 +3604,34 @@ void camera_table(const rt_camera& C, uint64_t seed, int spp, std::vector<float4
 // and returns the 256 key totals on the host; sort_scatter writes out[base[v] + rank] = k for every
 // key v (base: device array of 256, the caller's layout).
 constexpr int kOrderTabWords = 256 + 2 * kOrderKeys + 256;  // base, sub_ge, rest_gt, key totals
+// Room for n elements in the context's buffer b (DevBuf::reserve); *moved: it was freed and allocated
+// again -- or, with the error, is now empty -- so whatever described its contents no longer holds.
+template <class T>
+int reserve(rt_ctx* c, DevBuf<T>& b, long long n, const char* name, bool* moved = nullptr) {
+  const auto r = b.reserve((size_t)n);
+  if (moved) *moved = r != b.kept;
+  return r == b.failed ? fail(c, RT_ERR_HIP, std::string("out of device memory (") + name + ")") : RT_OK;
+}
+// The context's item schedule (perm, the long prefix, the split items and their claim order) no longer
+// belongs to a configuration: the one perm_key named runs cold again when it repeats.
+void drop_schedule(rt_ctx* c) {
+  c->perm_key.invalidate();
+  c->split_state = -1;
+  c->n_split = 0;
+  c->order_ok = false;
+}
 uint8_t* sort_keys(rt_ctx* c, long long n) {
   const long long tiles = (n + kOrderTile - 1) / kOrderTile;
   const long long need = ((n + 255) & ~255LL) + tiles * 256 * 4;
-  if (need > c->sort_scratch_cap) {
-    if (c->sort_scratch) (void)hipFree(c->sort_scratch);
-    c->sort_scratch = nullptr;
-    c->sort_scratch_cap = 0;
-    if (hipMalloc((void**)&c->sort_scratch, (size_t)need) != hipSuccess) return nullptr;
-    c->sort_scratch_cap = need;
-  }
-  if (!c->order_tab && hipMalloc((void**)&c->order_tab, kOrderTabWords * sizeof(unsigned)) != hipSuccess) return nullptr;
-  return c->sort_scratch;
+  if (c->sort_scratch.reserve((size_t)need) == c->sort_scratch.failed) return nullptr;
+  if (c->order_tab.reserve(kOrderTabWords) == c->order_tab.failed) return nullptr;
+  return c->sort_scratch.get();
 }
 int sort_hist(rt_ctx* c, long long n, unsigned hist[256]) {
   const unsigned tiles = (unsigned)((n + kOrderTile - 1) / kOrderTile);
-  unsigned* tile_tab = (unsigned*)(c->sort_scratch + ((n + 255) & ~255LL));
-  unsigned* totals = c->order_tab + 256 + 2 * kOrderKeys;
-  order_tile_hist_kernel<<<tiles, 64, 0, c->stream>>>(c->sort_scratch, (unsigned long long)n, tile_tab);
+  unsigned* tile_tab = (unsigned*)(c->sort_scratch.get() + ((n + 255) & ~255LL));
+  unsigned* totals = c->order_tab.get() + 256 + 2 * kOrderKeys;
+  order_tile_hist_kernel<<<tiles, 64, 0, c->stream>>>(c->sort_scratch.get(), (unsigned long long)n, tile_tab);
   HIPCHK(c, hipGetLastError());
   order_scan_kernel<<<256, 256, 0, c->stream>>>(tile_tab, tiles, totals);
   HIPCHK(c, hipGetLastError());
@@ -3620,8 +3641,8 @@ int sort_hist(rt_ctx* c, long long n, unsigned hist[256]) {
 }
 int sort_scatter(rt_ctx* c, long long n, const unsigned* base, uint32_t* out) {
   const unsigned tiles = (unsigned)((n + kOrderTile - 1) / kOrderTile);
-  const unsigned* tile_tab = (const unsigned*)(c->sort_scratch + ((n + 255) & ~255LL));
-  order_scatter_kernel<<<tiles, 64, 0, c->stream>>>(c->sort_scratch, (unsigned long long)n, tile_tab, base, out);
+  const unsigned* tile_tab = (const unsigned*)(c->sort_scratch.get() + ((n + 255) & ~255LL));
+  order_scatter_kernel<<<tiles, 64, 0, c->stream>>>(c->sort_scratch.get(), (unsigned long long)n, tile_tab, base, out);
   HIPCHK(c, hipGetLastError());
   return RT_OK;
 }
@@ -3693,10 +3714,10 @@ int build_schedule(rt_ctx* c, long long items, int spp, unsigned long long segs,
   if (!keys) return fail(c, RT_ERR_HIP, "out of device memory (schedule sort)");
   unsigned cmax = 0;
   {
-    unsigned* dmax = c->order_tab + 256 + 2 * kOrderKeys;  // key-total words, free until sort_hist
+    unsigned* dmax = c->order_tab.get() + 256 + 2 * kOrderKeys;  // key-total words, free until sort_hist
     HIPCHK(c, hipMemsetAsync(dmax, 0, sizeof(unsigned), c->stream));
     cost_max_kernel<<<(unsigned)std::min<long long>(1024, (items + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
-        c->item_cost, (unsigned long long)items, dmax);
+        c->item_cost.get(), (unsigned long long)items, dmax);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(&cmax, dmax, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3709,7 +3730,7 @@ int build_schedule(rt_ctx* c, long long items, int spp, unsigned long long segs,
   while (shift < 8 && (cmax >> shift) > (step_kernel ? 255u : 1023u)) ++shift;
   if (c->opt.cost_shift >= 0) shift = std::min(12, c->opt.cost_shift);  // tuning
   cost_key_kernel<<<(unsigned)((items + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
-      c->item_cost, (unsigned long long)items, shift, keys);
+      c->item_cost.get(), (unsigned long long)items, shift, keys);
   HIPCHK(c, hipGetLastError());
   unsigned h[256];
   if (int rc = sort_hist(c, items, h)) return rc;
@@ -3723,8 +3744,8 @@ int build_schedule(rt_ctx* c, long long items, int spp, unsigned long long segs,
       acc += h[v];
     }
   }
-  HIPCHK(c, hipMemcpyAsync(c->order_tab, base, sizeof(base), hipMemcpyHostToDevice, c->stream));
-  if (int rc = sort_scatter(c, items, c->order_tab, c->perm)) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->order_tab.get(), base, sizeof(base), hipMemcpyHostToDevice, c->stream));
+  if (int rc = sort_scatter(c, items, c->order_tab.get(), c->perm.get())) return rc;
   // completed before returning (base is on this stack): the next launch (same stream) reads perm
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const double pct = c->opt.long_pct;
@@ -3787,7 +3808,7 @@ __global__ __launch_bounds__(kBlock) void spread_head_kernel(const uint32_t* __r
   }
 }
 
-// Item schedule of a probe-scheduled first launch from the smoothed probe grid (c->probe_cost + pitems):
+// Item schedule of a probe-scheduled first launch from the smoothed probe grid (c->probe_cost.get() + pitems):
 // every step on the device, no host round trip (the draw's critical path): per-item keys, the tile
 // histograms and their scan, the bases, the stable scatter into perm.  The long prefix is the first
 // long_pct % of the positions.  Cost buckets of 8 segments, as the measured schedule's (natural order
@@ -3804,18 +3825,18 @@ int probe_schedule(rt_ctx* c, long long items, int spp, int width, int fbc, int 
   while (shift < 12 && ((32LL * spp) >> shift) > 255) ++shift;
   if (c->opt.cost_shift >= 0) shift = c->opt.cost_shift;  // tuning
   probe_keys_kernel<<<(unsigned)std::min<long long>(4096, (items + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
-      c->probe_cost + pitems, keys, (unsigned long long)items, width, fbc, spp, ps, pw, shift);
+      c->probe_cost.get() + pitems, keys, (unsigned long long)items, width, fbc, spp, ps, pw, shift);
   HIPCHK(c, hipGetLastError());
   const unsigned tiles = (unsigned)((items + kOrderTile - 1) / kOrderTile);
-  unsigned* tile_tab = (unsigned*)(c->sort_scratch + ((items + 255) & ~255LL));
-  unsigned* totals = c->order_tab + 256 + 2 * kOrderKeys;
+  unsigned* tile_tab = (unsigned*)(c->sort_scratch.get() + ((items + 255) & ~255LL));
+  unsigned* totals = c->order_tab.get() + 256 + 2 * kOrderKeys;
   order_tile_hist_kernel<<<tiles, 64, 0, c->stream>>>(keys, (unsigned long long)items, tile_tab);
   HIPCHK(c, hipGetLastError());
   order_scan_kernel<<<256, 256, 0, c->stream>>>(tile_tab, tiles, totals);
   HIPCHK(c, hipGetLastError());
-  key_base_kernel<<<1, 64, 0, c->stream>>>(totals, c->order_tab);
+  key_base_kernel<<<1, 64, 0, c->stream>>>(totals, c->order_tab.get());
   HIPCHK(c, hipGetLastError());
-  if (int rc = sort_scatter(c, items, c->order_tab, c->perm)) return rc;
+  if (int rc = sort_scatter(c, items, c->order_tab.get(), c->perm.get())) return rc;
   c->n_long = (unsigned long long)((double)items * c->opt.long_pct / 100.0);
   // Spread head (spread_top > 0, options.spread_first): longest first, the first claims would hand the
   // estimated-longest items 64 to a wave to the waves that claim first (one workgroup's); strided, every
@@ -3823,16 +3844,10 @@ int probe_schedule(rt_ctx* c, long long items, int spp, int width, int fbc, int 
   const int sf = spread_top;
   if (sf > 0 && waves > 0 && items >= 64 * waves) {
     const long long n = 64 * waves;
-    if (n > c->spread_cap) {
-      if (c->spread_tmp) HIPCHK(c, hipFree(c->spread_tmp));
-      c->spread_tmp = nullptr;
-      c->spread_cap = 0;
-      HIPCHK(c, hipMalloc((void**)&c->spread_tmp, (size_t)n * sizeof(uint32_t)));
-      c->spread_cap = n;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->spread_tmp, c->perm, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    if (int rc = reserve(c, c->spread_tmp, n, "spread head")) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->spread_tmp.get(), c->perm.get(), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     spread_head_kernel<<<(unsigned)std::min<long long>(4096, (n + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
-        c->spread_tmp, c->perm, (unsigned long long)waves, (unsigned)sf);
+        c->spread_tmp.get(), c->perm.get(), (unsigned long long)waves, (unsigned)sf);
     HIPCHK(c, hipGetLastError());
   }
   return RT_OK;
@@ -3892,12 +3907,13 @@ int rt_ctx_create(int hip_device, rt_ctx** out) {
   if (rc == RT_OK) chk(hipEventCreate(&c->ev0), "hipEventCreate");
   if (rc == RT_OK) chk(hipEventCreate(&c->ev1), "hipEventCreate");
   if (rc == RT_OK) chk(hipEventCreate(&c->ev2), "hipEventCreate");
-  if (rc == RT_OK) chk(hipMalloc((void**)&c->work, 8 * sizeof(unsigned long long)), "hipMalloc");
+  auto room = [&](bool ok) { chk(ok ? hipSuccess : hipErrorOutOfMemory, "hipMalloc"); };  // DevBuf::alloc
+  if (rc == RT_OK) room(c->work.alloc(8));
   if (rc == RT_OK) {
     std::vector<uint32_t> seq(32 * 800);
     rtx::build_sequence_jumps(seq.data());
-    chk(hipMalloc((void**)&c->seq, seq.size() * 4), "hipMalloc");
-    if (rc == RT_OK) chk(hipMemcpy(c->seq, seq.data(), seq.size() * 4, hipMemcpyHostToDevice), "hipMemcpy");
+    room(c->seq.alloc(seq.size()));
+    if (rc == RT_OK) chk(hipMemcpy(c->seq.get(), seq.data(), seq.size() * 4, hipMemcpyHostToDevice), "hipMemcpy");
     // byte tables of M^d for the 32 digit positions M = seq[i], d = 1..3
     std::vector<uint32_t> tab((size_t)96 * kTabMat, 0u);
     std::vector<uint32_t> m2(800), m3(800);
@@ -3915,8 +3931,8 @@ int rt_ctx_create(int hip_device, rt_ctx** out) {
                 for (int k = 0; k < 5; ++k) t[(b * 256 + v) * kTabRow + k] ^= ms[d][5 * (8 * b + j) + k];
       }
     }
-    if (rc == RT_OK) chk(hipMalloc((void**)&c->jump_tab, tab.size() * 4), "hipMalloc");
-    if (rc == RT_OK) chk(hipMemcpy(c->jump_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice), "hipMemcpy");
+    if (rc == RT_OK) room(c->jump_tab.alloc(tab.size()));
+    if (rc == RT_OK) chk(hipMemcpy(c->jump_tab.get(), tab.data(), tab.size() * 4, hipMemcpyHostToDevice), "hipMemcpy");
   }
   if (rc == RT_OK) {
     hipDeviceProp_t prop;
@@ -3941,29 +3957,6 @@ int rt_ctx_destroy(rt_ctx* c) {
   if (!c) return RT_OK;
   (void)hipSetDevice(c->device);
   free_scene(c);
-  if (c->states) (void)hipFree(c->states);
-  if (c->seq) (void)hipFree(c->seq);
-  if (c->jump_tab) (void)hipFree(c->jump_tab);
-  if (c->work) (void)hipFree(c->work);
-  if (c->row_map) (void)hipFree(c->row_map);
-  if (c->row_cost) (void)hipFree(c->row_cost);
-  if (c->item_cost) (void)hipFree(c->item_cost);
-  if (c->probe_cost) (void)hipFree(c->probe_cost);
-  if (c->spread_tmp) (void)hipFree(c->spread_tmp);
-  if (c->perm) (void)hipFree(c->perm);
-  if (c->dbg) (void)hipFree(c->dbg);
-  if (c->tiles) (void)hipFree(c->tiles);
-  if (c->cam_tab) (void)hipFree(c->cam_tab);
-  if (c->ckpt) (void)hipFree(c->ckpt);
-  if (c->order) (void)hipFree(c->order);
-  if (c->order_tab) (void)hipFree(c->order_tab);
-  if (c->sort_scratch) (void)hipFree(c->sort_scratch);
-  if (c->contrib) (void)hipFree(c->contrib);
-  if (c->cam_st) (void)hipFree(c->cam_st);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->ev2) (void)hipEventDestroy(c->ev2);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return RT_OK;
 }
@@ -4003,11 +3996,8 @@ int rt_ctx_set_options(rt_ctx* c, const rt_ctx_options* o) {
     return fail(c, RT_ERR_ARG, "bad context options");
   c->opt = *o;
   // the schedule and split thresholds come from the options: every configuration starts cold again
-  std::fill(c->perm_key, c->perm_key + rt_ctx::kKey, -1LL);
-  std::fill(c->pending_key, c->pending_key + rt_ctx::kKey, -1LL);
-  c->split_state = -1;
-  c->n_split = 0;
-  c->order_ok = false;
+  drop_schedule(c);
+  c->pending_key.invalidate();
   return RT_OK;
 }
 
@@ -4532,20 +4522,15 @@ int rt_render_init(rt_ctx* c, int32_t width, int32_t height, uint64_t seed) {
   if (!c || width <= 0 || height <= 0) return fail(c, RT_ERR_ARG, "bad init args");
   HIPCHK(c, hipSetDevice(c->device));
   const long long n = (long long)width * height;
-  if (n != c->states_n) {
-    if (c->states) HIPCHK(c, hipFree(c->states));
-    c->states = nullptr;
-    c->states_n = 0;
-    HIPCHK(c, hipMalloc((void**)&c->states, (size_t)n * 2 * sizeof(uint4)));
-    c->states_n = n;
-  }
+  if (int rc = reserve(c, c->states, 2 * n, "RNG states")) return rc;
+  c->states_n = n;
   int digits = 0;
   for (unsigned long long x = (unsigned long long)(n - 1); x; x >>= 2) ++digits;
   // one workgroup per CU (its LDS holds the 100 KB slot-step table), every lane a run of slots
   const long long blocks = std::max(1LL, std::min<long long>(c->cus, (n + kInitBlock - 1) / kInitBlock));
   const long long chunk = (n + blocks * kInitBlock - 1) / (blocks * kInitBlock);
   hipLaunchKernelGGL(init_states_kernel, dim3((unsigned)blocks), dim3(kInitBlock), 5 * kStepRows * sizeof(uint32_t),
-                     c->stream, c->states, n, seed, (const uint32_t*)c->jump_tab, digits, chunk);
+                     c->stream, c->states.get(), n, seed, (const uint32_t*)c->jump_tab.get(), digits, chunk);
   HIPCHK(c, hipGetLastError());
   // no host wait: every reader of the states (rt_render's kernels, rt_read_states) is ordered
   // after this launch on the context's stream
@@ -4559,98 +4544,68 @@ int rt_render(rt_ctx* c, const rt_render_args* a, float* fb, rt_counters* counte
   if (rc) return rc;
   if (!fb) return fail(c, RT_ERR_ARG, "null fb");
   HIPCHK(c, hipSetDevice(c->device));
-  if (device_ptr(fb)) return render_dev(c, a, fb, counters);
   // host frame buffer: render into device memory, then copy the owned rows back
-  const size_t n = (size_t)a->fb_count * rt_owned_rows(a, nullptr) * a->width * 3;
-  float* tmp = nullptr;
-  HIPCHK(c, hipMalloc((void**)&tmp, n * sizeof(float)));
-  rc = render_dev(c, a, tmp, counters);
-  if (!rc && hipMemcpy(fb, tmp, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+  const Staged<float> st(fb, (size_t)a->fb_count * rt_owned_rows(a, nullptr) * a->width * 3);
+  if (!st.ok()) return fail(c, RT_ERR_HIP, "out of device memory (host frame buffer)");
+  rc = render_dev(c, a, st.dev(), counters);
+  if (!rc && st.host() && hipMemcpy(fb, st.dev(), st.bytes(), hipMemcpyDeviceToHost) != hipSuccess)
     rc = fail(c, RT_ERR_HIP, "copy frame buffer to host");
-  (void)hipFree(tmp);
   return rc;
 }
 
 }  // extern "C"
 
-// tl (a tile launch): the launch claims tl's items in tl's order and is isolated from the context's
-// schedule state -- no schedule is read, built or recorded (perm_key, pending_key, the split state and
-// host_cost / cost_key stay as they are; the schedule flags have no effect), no probe, no split samples,
-// n_long = 0, no item or row costs, rows in ascending order (the row-map cache is kept up to date).
-int rtctx::render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* counters, const TileLaunch* tl) {
-  int rc = RT_OK;
-  if (!c->have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
-  if (!c->states || c->states_n != (long long)a->width * a->height || c->states_seed != a->seed)
-    return fail(c, RT_ERR_STATE, "rt_render_init not called for this size/seed");
-  if (!fb_dev) return fail(c, RT_ERR_ARG, "null fb");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int rows = rt_owned_rows(a, nullptr);
-  if (rows <= 0) return fail(c, RT_ERR_ARG, "no rows owned");
-  if (rows > c->row_cap) {
-    if (c->row_map) HIPCHK(c, hipFree(c->row_map));
-    c->row_map = nullptr;
-    HIPCHK(c, hipMalloc((void**)&c->row_map, 2 * (size_t)rows * sizeof(int32_t)));
-    c->row_map_host.clear();
-    c->row_cap = rows;
-  }
-  if (a->height > c->row_cost_cap) {
-    if (c->row_cost) HIPCHK(c, hipFree(c->row_cost));
-    c->row_cost = nullptr;
-    HIPCHK(c, hipMalloc((void**)&c->row_cost, (size_t)a->height * sizeof(unsigned long long)));
-    c->row_cost_cap = a->height;
-  }
-  std::vector<int32_t> rm(2 * (size_t)rows);
+// ---------------------------------------------------------------- the stages of render_dev, in its order
+namespace {
+
+// One render_dev call: what its stages hand on to each other.
+struct Launch {
+  Launch(const rt_render_args* a_, const TileLaunch* tl_) : a(a_), tl(tl_) {}
+  const rt_render_args* a;
+  const TileLaunch* tl;
+  int rows = 0;              // owned
+  long long items = 0;       // (fb, pixel) pairs of the owned rows
+  bool step_kernel = false;  // the launch runs render_step_kernel (as pick_kernel decides): the schedules' cost buckets
+  bool sched = false;        // the launch may read, build and record the item schedule
+  Key<rt_ctx::kKey> pkey;
+  std::vector<int32_t> rm;  // [0, rows): the owned image rows; [rows, 2 rows): their processing order
+  Key<5> cost_key;
+  bool have_cost = false, measure_rows = false;  // row_tables
+  bool have_perm = false;                        // schedule_state
+  int split_mode = 0;                            // split_samples: 1 records, 2 replays
+  bool probe = false;                            // probe_grid: every ps-th owned row position and pixel
+  int ps = 0, prow = 0, pw = 0;
+  long long pitems = 0;
+};
+// The kernel of a launch (pick_kernel).
+struct KernelChoice {
+  int var = -1, mask = 0, bs = 0;  // index into kVariants, its feature mask, its block size
+  size_t shmem = 0;
+  int bpc = 0;          // resident workgroups per CU
+  double lanes = 0.0;   // resident lanes of the device
+  unsigned blocks = 0;  // the grid
+};
+long long item_cap(const rt_ctx* c) { return (long long)std::min(c->item_cost.size(), c->perm.size()); }
+// Row tables and the row-cost state: L.rm, L.have_cost, L.measure_rows; the row map on the device and the
+// work counters zeroed.
+int row_tables(rt_ctx* c, Launch& L) {
+  const rt_render_args* a = L.a;
+  const int rows = L.rows;
+  bool moved = false;
+  int rc = reserve(c, c->row_map, 2LL * rows, "row map", &moved);
+  if (moved) c->row_map_host.clear();
+  if (rc || (rc = reserve(c, c->row_cost, a->height, "row costs"))) return rc;
+  std::vector<int32_t>& rm = L.rm;
+  rm.resize(2 * (size_t)rows);
   rt_owned_rows(a, rm.data());
-  const long long key[5] = {c->scene_gen, a->width, a->height, a->spp, a->max_depth};
-  const bool have_cost = !tl && std::equal(key, key + 5, c->cost_key) && (int)c->host_cost.size() == a->height;
+  L.cost_key = {c->scene_gen, a->width, a->height, a->spp, a->max_depth};
+  L.have_cost = !L.tl && L.cost_key == c->cost_key && (int)c->host_cost.size() == a->height;
   for (int q = 0; q < rows; ++q) rm[rows + q] = q;
   // Costliest rows first only when lanes get few items each (a rank's share of a multi-GPU
   // image): there the launch ends with its last long item; with many items per lane bottom-to-top
   // order (sky last in the reference's scenes) measures faster.
-  const long long items = (long long)a->fb_count * rows * a->width;
-  // Item schedule: the first launch of a configuration records every item's segment count; later
-  // launches process the items longest first (cost buckets of 8 segments, natural order inside a
-  // bucket), and waves holding one of the top ~2 % run at raised priority.  A lane runs an item's samples serially, so
-  // an item that starts late under full load (22 us per segment per lane on C2) decides when a
-  // small share (a rank of a multi-GPU run) ends.  Pixel results do not depend on the order.
-  // cam_mode is part of the key: the split samples' recorded sample-start states depend on it (the
-  // PER_PIXEL camera draws come from the pixel's own state, REF ones from the slot-0 copy)
-  constexpr int K = rt_ctx::kKey;
-  // the launch runs render_step_kernel (as pick_variant decides below): the schedules' cost buckets
-  const bool step_kernel = (c->world_step || c->world_tree) && (a->flags & (RT_FLAG_NO_STEP | RT_FLAG_WIDEST)) == 0;
-  const long long pkey[K] = {c->scene_gen, a->width,   a->height,    a->spp,       a->max_depth, a->fb_first,
-                             a->fb_count,  a->band_rows, a->band_first, a->band_stride, a->cam_mode};
-  // (up to 2^31 items: 6 bytes of cost and position per item, C5's configured 100 fb x 100 spp draw
-  // has 829 M; perm holds 32-bit positions)
-  const bool sched = !tl && items <= (1LL << 31) && (a->flags & RT_FLAG_NO_SCHEDULE) == 0;
-  if (!tl && (a->flags & RT_FLAG_FRESH) != 0) {  // as the configuration's first launch
-    std::fill(c->perm_key, c->perm_key + K, -1LL);
-    std::fill(c->pending_key, c->pending_key + K, -1LL);
-    c->split_state = -1;
-    c->n_split = 0;
-    c->order_ok = false;
-  }
-  if (sched && !std::equal(pkey, pkey + K, c->perm_key) && std::equal(pkey, pkey + K, c->pending_key) &&
-      items <= c->item_cap) {  // the configuration repeats: its schedule from the measured counts
-    if ((rc = build_schedule(c, items, a->spp, c->pending_segs, step_kernel))) return rc;
-    std::copy(pkey, pkey + K, c->perm_key);
-    std::fill(c->pending_key, c->pending_key + K, -1LL);
-  }
-  const bool have_perm = sched && std::equal(pkey, pkey + K, c->perm_key);
-  if (sched && items > c->item_cap) {
-    if (c->item_cost) HIPCHK(c, hipFree(c->item_cost));
-    if (c->perm) HIPCHK(c, hipFree(c->perm));
-    c->item_cost = nullptr;
-    c->perm = nullptr;
-    c->item_cap = 0;
-    std::fill(c->perm_key, c->perm_key + K, -1LL);
-    std::fill(c->pending_key, c->pending_key + K, -1LL);
-    HIPCHK(c, hipMalloc((void**)&c->item_cost, (size_t)items * sizeof(uint16_t)));
-    HIPCHK(c, hipMalloc((void**)&c->perm, (size_t)items * sizeof(uint32_t)));
-    c->item_cap = items;
-  }
   const long long order_cap = 8LL * c->cus * 1024;
-  if (!sched && have_cost && items < order_cap)
+  if (!L.sched && L.have_cost && L.items < order_cap)
     std::stable_sort(rm.begin() + rows, rm.end(), [&](int x, int y) { return c->host_cost[rm[x]] > c->host_cost[rm[y]]; });
   // Per-launch host work kept off the repeat path: the row tables are uploaded only when they
   // change, the row costs are cleared and read back only on their measuring launch.
@@ -4661,27 +4616,80 @@ int rtctx::render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_coun
   }
   if (rq != c->row_map_host) {
     c->row_map_host = rq;  // kept alive for the async copy
-    HIPCHK(c, hipMemcpyAsync(c->row_map, c->row_map_host.data(), 2 * (size_t)rows * sizeof(int32_t),
+    HIPCHK(c, hipMemcpyAsync(c->row_map.get(), c->row_map_host.data(), 2 * (size_t)rows * sizeof(int32_t),
                              hipMemcpyHostToDevice, c->stream));
   }
-  HIPCHK(c, hipMemsetAsync(c->work, 0, 8 * sizeof(unsigned long long), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->work.get(), 0, 8 * sizeof(unsigned long long), c->stream));
   // row costs order the rows only when there is no item schedule: measured only then
-  const bool measure_rows = !tl && !have_cost && !sched;
-  if (measure_rows) HIPCHK(c, hipMemsetAsync(c->row_cost, 0, (size_t)a->height * sizeof(unsigned long long), c->stream));
-
-  RenderParams P{};
+  L.measure_rows = !L.tl && !L.have_cost && !L.sched;
+  if (L.measure_rows)
+    HIPCHK(c, hipMemsetAsync(c->row_cost.get(), 0, (size_t)a->height * sizeof(unsigned long long), c->stream));
+  return RT_OK;
+}
+// Item schedule: the first launch of a configuration records every item's segment count; later
+// launches process the items longest first (cost buckets of 8 segments, natural order inside a
+// bucket), and waves holding one of the top ~2 % run at raised priority.  A lane runs an item's samples serially, so
+// an item that starts late under full load (22 us per segment per lane on C2) decides when a
+// small share (a rank of a multi-GPU run) ends.  Pixel results do not depend on the order.
+// This stage: RT_FLAG_FRESH, the schedule of a repeating configuration, L.have_perm, room for the items.
+int schedule_state(rt_ctx* c, Launch& L) {
+  const rt_render_args* a = L.a;
+  if (!L.tl && (a->flags & RT_FLAG_FRESH) != 0) {  // as the configuration's first launch
+    drop_schedule(c);
+    c->pending_key.invalidate();
+  }
+  if (L.sched && L.pkey != c->perm_key && L.pkey == c->pending_key &&
+      L.items <= item_cap(c)) {  // the configuration repeats: its schedule from the measured counts
+    if (int rc = build_schedule(c, L.items, a->spp, c->pending_segs, L.step_kernel)) return rc;
+    c->perm_key = L.pkey;
+    c->pending_key.invalidate();
+  }
+  L.have_perm = L.sched && L.pkey == c->perm_key;
+  if (!L.sched) return RT_OK;
+  bool moved_cost = false, moved_perm = false;
+  int rc = reserve(c, c->item_cost, L.items, "item costs", &moved_cost);
+  if (!rc) rc = reserve(c, c->perm, L.items, "item order", &moved_perm);
+  if (moved_cost || moved_perm) {  // what was measured or ordered is gone
+    c->perm_key.invalidate();
+    c->pending_key.invalidate();
+  }
+  return rc;
+}
+// camera_table's per-sample lens offsets and times (REF camera rays), or its sample-start states.
+void sample_table(const rt_camera& C, uint64_t seed, int spp, std::vector<float4>& out) { camera_table(C, seed, spp, out); }
+void sample_table(const rt_camera& C, uint64_t seed, int spp, std::vector<uint4>& out) {
+  std::vector<float4> unused;
+  camera_table(C, seed, spp, unused, &out);
+}
+// The per-sample camera table of (scene, seed, spp) in buf: computed and uploaded when key names another
+// one (host stays alive while the upload is in flight).
+template <class T>
+int camera_samples(rt_ctx* c, const rt_render_args* a, Key<3>& key, DevBuf<T>& buf, std::vector<T>& host, const char* name) {
+  const Key<3> now = {c->scene_gen, a->seed, a->spp};
+  if (now == key) return RT_OK;
+  key.invalidate();
+  sample_table(c->scene.cam, a->seed, a->spp, host);
+  if (int rc = reserve(c, buf, (long long)host.size(), name)) return rc;
+  HIPCHK(c, hipMemcpyAsync(buf.get(), host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
+  key = now;
+  return RT_OK;
+}
+// RenderParams from the arguments and the stages before: the image, the rows, the schedule's order, the
+// REF camera table, the audit log.
+int render_params(rt_ctx* c, const Launch& L, float* fb_dev, RenderParams& P) {
+  const rt_render_args* a = L.a;
   P.S = c->scene;
-  P.states = c->states;
+  P.states = c->states.get();
   P.fb = fb_dev;
-  P.row_q = (const int2*)c->row_map;
-  P.row_cost = measure_rows ? c->row_cost : nullptr;  // measured once per configuration
-  P.work = c->work;
-  P.counters = c->work + 1;
-  P.total_items = tl ? tl->n_items : (unsigned long long)a->fb_count * rows * a->width;
+  P.row_q = (const int2*)c->row_map.get();
+  P.row_cost = L.measure_rows ? c->row_cost.get() : nullptr;  // measured once per configuration
+  P.work = c->work.get();
+  P.counters = c->work.get() + 1;
+  P.total_items = L.tl ? L.tl->n_items : (unsigned long long)L.items;
   P.npix = (long long)a->width * a->height;
   P.W = a->width;
   P.H = a->height;
-  P.rows = rows;
+  P.rows = L.rows;
   P.pstep = 1;
   P.per_row = (long long)a->fb_count * a->width;
   P.spp = a->spp;
@@ -4693,26 +4701,28 @@ int rtctx::render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_coun
   P.cam_state[0] = cs.d;
   for (int k = 0; k < 5; ++k) P.cam_state[1 + k] = cs.v[k];
   if (a->cam_mode == RT_CAM_REF_SLOT0) {
-    const long long ckey[3] = {c->scene_gen, (long long)a->seed, a->spp};
-    if (!std::equal(ckey, ckey + 3, c->cam_key)) {
-      if (a->spp > c->cam_cap) {
-        if (c->cam_tab) HIPCHK(c, hipFree(c->cam_tab));
-        c->cam_tab = nullptr;
-        c->cam_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->cam_tab, (size_t)a->spp * sizeof(float4)));
-        c->cam_cap = a->spp;
-      }
-      camera_table(c->scene.cam, a->seed, a->spp, c->cam_host);
-      HIPCHK(c, hipMemcpyAsync(c->cam_tab, c->cam_host.data(), (size_t)a->spp * sizeof(float4), hipMemcpyHostToDevice,
-                               c->stream));
-      std::copy(ckey, ckey + 3, c->cam_key);
-    }
-    P.S.cam_tab = c->cam_tab;
+    if (int rc = camera_samples(c, a, c->cam_key, c->cam_tab, c->cam_host, "camera table")) return rc;
+    P.S.cam_tab = c->cam_tab.get();
   }
-
+  P.perm = L.tl ? L.tl->perm : (L.have_perm ? c->perm.get() : nullptr);
+  P.n_long = L.have_perm ? c->n_long : 0;
+  P.item_cost = (L.sched && !L.have_perm) ? c->item_cost.get() : nullptr;
+  if ((a->flags & RT_FLAG_AUDIT) != 0) {
+    if (int rc = reserve(c, c->dbg, 16LL * kAuditCap + 16, "audit log")) return rc;
+    HIPCHK(c, hipMemsetAsync(c->dbg.get(), 0, c->dbg.bytes(), c->stream));
+    P.S.dbg = c->dbg.get() + 16;
+    P.S.dbg_n = (unsigned*)c->dbg.get();
+    P.S.dbg_cap = kAuditCap;
+  }
+  return RT_OK;
+}
+// The kernel variant of the launch, its LDS layout (written to S.lds_*) and its grid; P.shade_min.
+int pick_kernel(rt_ctx* c, const Launch& L, RenderParams& P, KernelChoice& K) {
+  const rt_render_args* a = L.a;
+  DScene& S = P.S;
   const bool stats = a->stats != 0;
   const bool check = (a->flags & RT_FLAG_AUDIT) != 0;
-  const bool step = (c->world_step || c->world_tree) && (a->flags & (RT_FLAG_NO_STEP | RT_FLAG_WIDEST)) == 0;
+  const bool step = L.step_kernel;
   // node slots of the LDS image: the stepwise variant's world tree in planes of kPlanePairs records
   const int lds_node_slots = step && c->world_step ? (c->plane_fb >= 0 ? c->plane_fb + 2 * kPlanePairs : -1) : c->dev_nodes;
   const size_t lds_bytes =
@@ -4728,170 +4738,40 @@ int rtctx::render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_coun
   const size_t table_bytes = (size_t)16 * ((size_t)c->dev_mats + 2 * (size_t)c->dev_texs + (size_t)c->dev_imgs);
   const bool big_tables = table_bytes > 32768;
   const bool merge_tables_fit = table_bytes <= 1024;
-  int var = pick_variant(c->features, stats, (a->flags & RT_FLAG_EXACT_TRAVERSAL) != 0, check, use_lds,
-                         (a->flags & RT_FLAG_WIDEST) != 0, step, c->world_tree, qlds,
-                         c->scene.merge_ok != 0 && merge_tables_fit);
+  auto pick = [&](bool widest, bool merge) {
+    return pick_variant(c->features, stats, (a->flags & RT_FLAG_EXACT_TRAVERSAL) != 0, check, use_lds, widest, step,
+                        c->world_tree, qlds, merge);
+  };
+  int var = pick((a->flags & RT_FLAG_WIDEST) != 0, c->scene.merge_ok != 0 && merge_tables_fit);
   if (var >= 0 && big_tables && (kVariants[var].mask & (F_LDS | F_QLDS | F_STEP | F_BVH | F_TRI)) == 0)
-    var = pick_variant(c->features, stats, (a->flags & RT_FLAG_EXACT_TRAVERSAL) != 0, check, use_lds, true, step,
-                       c->world_tree, qlds, c->scene.merge_ok != 0);
+    var = pick(true, c->scene.merge_ok != 0);
   if (var < 0) return fail(c, RT_ERR_SCENE, "no kernel variant covers the scene features");
+  const int mask = kVariants[var].mask;
   // shading phase of render_step_kernel once this many lanes of a wave wait (RT_SHADE_MIN: tuning)
   // (measured: C2 best at 60 of 64 lanes; C4's triangle-mesh steps at 48: 125.0 -> 119.7 ms, 40: 121.8)
   // (round 4, after the triangle dedupe and two steps per check, C4 Mrays/s at 40/48/52/56/60/62: 13 490 /
   // 13 922 / 14 052 / 14 090 / 13 932 / 13 618; C2 at 56/60/62: 14 659 / 14 747 / 14 605)
-  P.shade_min = (kVariants[var].mask & F_TRI) != 0 ? kShadeMinMesh : kShadeMin;
-  P.perm = tl ? tl->perm : (have_perm ? c->perm : nullptr);
-  P.n_long = have_perm ? c->n_long : 0;
-  // Split samples of the longest items (stepwise kernel; scheduled launches of a configuration
-  // with split items): the launch after the measuring one records their sample-start RNG states,
-  // later launches with the same seed run each of their samples as a separate work item.
-  // (split samples: the stepwise kernel, and render_kernel's parking variants)
-  const bool split_ok = have_perm && c->n_split > 0 && a->spp > 1 && (a->flags & RT_FLAG_NO_SPLIT) == 0 &&
-                        ((kVariants[var].mask & F_STEP) != 0 || parks_segment_mask(kVariants[var].mask));
-  int split_mode = 0;
-  if (split_ok && c->split_state == 1 && c->split_seed == a->seed) split_mode = 2;
-  else if (split_ok) split_mode = 1;
-  if (split_mode != 0) {
-    const long long need = (long long)c->n_split * a->spp;
-    if (need > c->ckpt_cap) {
-      if (c->ckpt) HIPCHK(c, hipFree(c->ckpt));
-      c->ckpt = nullptr;
-      c->ckpt_cap = 0;
-      c->split_state = -1;
-      HIPCHK(c, hipMalloc((void**)&c->ckpt, (size_t)need * 2 * sizeof(uint4)));
-      c->ckpt_cap = need;
-      split_mode = 1;
-    }
-    if (split_mode == 2 && 3 * need > c->contrib_cap) {
-      if (c->contrib) HIPCHK(c, hipFree(c->contrib));
-      c->contrib = nullptr;
-      c->contrib_cap = 0;
-      HIPCHK(c, hipMalloc((void**)&c->contrib, (size_t)need * 3 * sizeof(float)));
-      c->contrib_cap = 3 * need;
-    }
-    const long long skey[3] = {c->scene_gen, (long long)a->seed, a->spp};
-    if (!std::equal(skey, skey + 3, c->cam_st_key)) {  // REF camera state at every sample start
-      if (a->spp > c->cam_st_cap) {
-        if (c->cam_st) HIPCHK(c, hipFree(c->cam_st));
-        c->cam_st = nullptr;
-        c->cam_st_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->cam_st, (size_t)a->spp * 2 * sizeof(uint4)));
-        c->cam_st_cap = a->spp;
-      }
-      std::vector<float4> unused;
-      camera_table(c->scene.cam, a->seed, a->spp, unused, &c->cam_st_host);
-      HIPCHK(c, hipMemcpyAsync(c->cam_st, c->cam_st_host.data(), c->cam_st_host.size() * sizeof(uint4),
-                               hipMemcpyHostToDevice, c->stream));
-      std::copy(skey, skey + 3, c->cam_st_key);
-    }
-    // Split launches claim split samples and unsplit items in one sequence, longest first by the
-    // recording launch's counts (the long samples of a small share start with the launch instead of
-    // trailing it).  Built once per recording; results do not depend on the order.
-    const long long rest = items - (long long)c->n_split;
-    if (split_mode == 2 && c->rest_n == rest && c->opt.split_order != 0) {  // 0: samples in item order, then the rest
-      const long long total = need + rest;
-      if (!c->order_ok) {
-        if (total > c->order_cap) {
-          if (c->order) HIPCHK(c, hipFree(c->order));
-          c->order = nullptr;
-          c->order_cap = 0;
-          HIPCHK(c, hipMalloc((void**)&c->order, (size_t)total * sizeof(uint32_t)));
-          c->order_cap = total;
-        }
-        uint8_t* len = sort_keys(c, need);
-        if (!len) return fail(c, RT_ERR_HIP, "out of device memory (split order)");
-        split_len_kernel<<<(unsigned)((need + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
-            c->ckpt, (unsigned long long)need, a->spp, len);
-        HIPCHK(c, hipGetLastError());
-        unsigned hist[256];
-        if ((rc = sort_hist(c, need, hist))) return rc;
-        std::vector<unsigned>& t = c->order_tab_host;
-        t.assign(256 + 2 * kOrderKeys, 0u);
-        unsigned* sub_base = t.data();
-        unsigned* sub_ge = t.data() + 256;
-        unsigned* rest_gt = t.data() + 256 + kOrderKeys;
-        for (int v = 255; v >= 0; --v) sub_ge[v] = sub_ge[v + 1] + hist[v];  // sub_ge[256] = 0
-        for (int v = 0; v < 256; ++v) sub_base[v] = c->rest_gt[(size_t)v] + sub_ge[v + 1];
-        std::copy(c->rest_gt.begin(), c->rest_gt.end(), rest_gt);
-        HIPCHK(c, hipMemcpyAsync(c->order_tab, t.data(), t.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
-        if ((rc = sort_scatter(c, need, c->order_tab, c->order))) return rc;
-        if (rest > 0) {
-          order_rest_kernel<<<(unsigned)((rest + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
-              (unsigned long long)need, (unsigned long long)rest, c->order_tab, c->order);
-          HIPCHK(c, hipGetLastError());
-        }
-        c->order_ok = true;
-      }
-      P.order = c->order;
-    }
-    P.split_mode = split_mode;
-    P.n_split = c->n_split;
-    P.ckpt = c->ckpt;
-    P.contrib = c->contrib;
-    P.cam_st = c->cam_st;
-    if (split_mode == 2) P.total_items = (unsigned long long)need + (unsigned long long)(items - (long long)c->n_split);
-  }
-  P.item_cost = (sched && !have_perm) ? c->item_cost : nullptr;
+  P.shade_min = (mask & F_TRI) != 0 ? kShadeMinMesh : kShadeMin;
   if (c->opt.shade_min > 0) P.shade_min = c->opt.shade_min;
-  if (check) {
-    if (!c->dbg) {
-      HIPCHK(c, hipMalloc((void**)&c->dbg, 16 * sizeof(float) * kAuditCap + 64));
-    }
-    HIPCHK(c, hipMemsetAsync(c->dbg, 0, 16 * sizeof(float) * kAuditCap + 64, c->stream));
-    P.S.dbg = c->dbg + 16;
-    P.S.dbg_n = (unsigned*)c->dbg;
-    P.S.dbg_cap = kAuditCap;
-  }
   const int bs = variant_block(var);
-  const bool lds_var = (kVariants[var].mask & F_LDS) != 0;
-  const bool planes_var = lds_var && (kVariants[var].mask & F_STEP) != 0;
+  const bool lds_var = (mask & F_LDS) != 0;
+  const bool planes_var = lds_var && (mask & F_STEP) != 0;
   if (planes_var && (c->plane_fb < 0 || lds_node_slots != c->plane_fb + 2 * kPlanePairs))
     return fail(c, RT_ERR_STATE, "stepwise LDS variant without a plane-staged world tree");
-  P.S.lds_nodes = lds_var ? (planes_var ? lds_node_slots : c->dev_nodes) : 0;
-  P.S.lds_fb = planes_var ? c->plane_fb : 0;
-  P.S.lds_pairs = planes_var ? c->plane_pairs : 0;
-  P.S.lds_prims = lds_var ? c->dev_prims : 0;
-  const bool qlds_var = (kVariants[var].mask & F_QLDS) != 0;
-  const int vmask = kVariants[var].mask;
-  const bool tables_var = (vmask & (F_LDS | F_QLDS | F_STEP | F_BVH | F_TRI)) == 0 || (vmask & F_MERGE) != 0;
-  P.S.lds_mats = (lds_var || qlds_var || tables_var) ? c->dev_mats : 0;
-  P.S.lds_texs = (lds_var || qlds_var || tables_var) ? c->dev_texs : 0;
-  P.S.lds_imgs = (qlds_var || tables_var) ? c->dev_imgs : 0;
+  S.lds_nodes = lds_var ? (planes_var ? lds_node_slots : c->dev_nodes) : 0;
+  S.lds_fb = planes_var ? c->plane_fb : 0;
+  S.lds_pairs = planes_var ? c->plane_pairs : 0;
+  S.lds_prims = lds_var ? c->dev_prims : 0;
+  const bool qlds_var = (mask & F_QLDS) != 0;
+  const bool tables_var = (mask & (F_LDS | F_QLDS | F_STEP | F_BVH | F_TRI)) == 0 || (mask & F_MERGE) != 0;
+  S.lds_mats = (lds_var || qlds_var || tables_var) ? c->dev_mats : 0;
+  S.lds_texs = (lds_var || qlds_var || tables_var) ? c->dev_texs : 0;
+  S.lds_imgs = (qlds_var || tables_var) ? c->dev_imgs : 0;
   static_assert(kStackDepthQ == kStackDepth, "F_QLDS stacks");
   const size_t shmem = lds_var    ? lds_bytes + (size_t)bs * kStackDepth * 2
-                       : qlds_var ? (size_t)16 * (qlds_mats_at(P.S) + c->dev_mats + 2 * c->dev_texs + c->dev_imgs)
-                                  : (size_t)bs * (stack_words(vmask) + locker_words(vmask)) * 4 +
+                       : qlds_var ? (size_t)16 * (qlds_mats_at(S) + c->dev_mats + 2 * c->dev_texs + c->dev_imgs)
+                                  : (size_t)bs * (stack_words(mask) + locker_words(mask)) * 4 +
                                         (tables_var ? table_bytes : 0);
-  // Camera-ray culling, built once per (scene, W, H): candidate lists for the stepwise kernel
-  // (world = one BVH), top-level entry masks for list worlds.  Not in the exact / audit modes,
-  // whose counters are the reference's.
-  const int vm = kVariants[var].mask;
-  const bool cull = (a->flags & RT_FLAG_NO_CAMERA_BINS) == 0 && (vm & (F_EXACT | F_CHECK)) == 0;
-  const int tx = (a->width + (1 << kTileShift) - 1) >> kTileShift, ty = (a->height + (1 << kTileShift) - 1) >> kTileShift;
-  const long long nt = (long long)tx * ty, ntp = (nt + 3) & ~3LL;  // tile lists: counts, then entries from ntp
-  if (cull && (vm & F_STEP) == 0 && c->bin_n < 0) {
-    const long long tkey[3] = {c->scene_gen, a->width, -1 - (long long)a->height};
-    if (!std::equal(tkey, tkey + 3, c->tiles_key)) {
-      if (nt > c->tiles_cap) {
-        if (c->tiles) HIPCHK(c, hipFree(c->tiles));
-        c->tiles = nullptr;
-        c->tiles_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->tiles, (size_t)nt * sizeof(int32_t)));
-        c->tiles_cap = nt;
-      }
-      bin_masks_kernel<<<(unsigned)((nt + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
-          c->bin_sph, -c->bin_n, c->scene.cam, a->width, a->height, tx, ty, (uint32_t*)c->tiles);
-      HIPCHK(c, hipGetLastError());
-      std::copy(tkey, tkey + 3, c->tiles_key);
-    }
-    P.tile_mask = (const uint32_t*)c->tiles;
-    P.tiles_x = tx;
-  }
-  // Camera-ray candidate lists pay when lanes get many items each; for a small share (a rank of a
-  // multi-GPU image) the launch ends with its longest items and the lists made that tail longer
-  // (C2, one GPU rendering each rank's share: N = 4 (9.2 items per resident lane) 5.24 ms with
-  // lists vs 5.94 without, N = 8 (4.6 per lane) 4.03 vs 3.51 ms).
-  const double bins_min = c->opt.bins_min_items_per_lane;  // items per resident lane (default 6)
   // resident workgroups per CU: from the context's occupancy table, except for the variants whose
   // LDS holds the scene's tables after the locker (their size is the scene's)
   int bpc = std::max(1, c->blocks_per_cu[var]);
@@ -4900,147 +4780,242 @@ int rtctx::render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_coun
     HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kVariants[var].fn, bs, shmem));
     bpc = std::max(1, b);
   }
-  const double lanes = (double)c->cus * bpc * bs;
-  if (cull && (vm & F_STEP) != 0 && c->bin_n > 0 && (double)P.total_items >= bins_min * lanes) {
-    const long long tkey[3] = {c->scene_gen, a->width, a->height};
-    if (!std::equal(tkey, tkey + 3, c->tiles_key)) {
-      if (ntp + nt * kTileCap * 2 > c->tiles_cap) {
-        if (c->tiles) HIPCHK(c, hipFree(c->tiles));
-        c->tiles = nullptr;
-        c->tiles_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->tiles, (size_t)(ntp + nt * kTileCap * 2) * sizeof(int32_t)));
-        c->tiles_cap = ntp + nt * kTileCap * 2;
-      }
-      bin_tiles_kernel<<<(unsigned)((nt + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
-          c->bin_sph, c->bin_ids, c->bin_n, c->scene.cam, a->width, a->height, tx, ty, c->tiles, c->tiles + ntp);
-      HIPCHK(c, hipGetLastError());
-      std::copy(tkey, tkey + 3, c->tiles_key);
-    }
-    P.tile_cnt = c->tiles;
-    P.tile_ent = c->tiles + ntp;  // 16-byte aligned: tile_candidates reads int4 groups
-    P.tiles_x = tx;
-    P.tile_cap = kTileCap;
-  }
   const long long resident = (long long)c->cus * bpc;
   // Persistent grid: every resident workgroup, even when there are fewer items than lanes (a
   // rank of a multi-GPU run): waves take items dynamically, so the items spread over all CUs
   // instead of packing into the first ceil(items / block) of them.
-  const unsigned blocks = (unsigned)std::max(1LL, resident);
-  // The first launch of a configuration has no measured item costs; a probe launch estimates them:
-  // sample 0 of the first fb (the item's own first sample: same state, same camera draw) at every
-  // ps-th owned row position and pixel, into the frame buffer's first fb slice, which the launch then
-  // overwrites.  An item's estimate is the mean count of the grid points within kProbeRadius of its
-  // own (rows and pixels) times spp; the launch claims items longest first by it (and records the
-  // real counts, from which the next launch builds the schedule).  Inside the timed region: the
-  // probe is part of the draw.  Grid step (options.probe_schedule < 0, the default): the smallest
-  // with step^2 * spp * fb_count >= 200, a probe of at most ~0.5 % of the draw's samples.  Measured
-  // (MI355X, cold first launches, no probe -> probe): whole frames C4 77.3 -> 67.0 ms (step 1; 4:
-  // 69.6), C5 67.8 -> 64.0 (step 4; 2: 65.1, 8: 64.8), C2 17.02 -> 16.96 (step 4; 1: 17.28); not for
-  // scenes without BVHs: C3's list of rects and media lost at every share size (N = 1 / 2 / 4 / 8
-  // 14.73 / 8.10 / 4.93 / 3.23 -> 15.64 / 8.94 / 5.70 / 4.04 ms), its costs short and spatially
-  // random, the natural order's coherence better (profiles/r05/probe/).
+  K = KernelChoice{var, mask, bs, shmem, bpc, (double)c->cus * bpc * bs, (unsigned)std::max(1LL, resident)};
+  return RT_OK;
+}
+// Split samples of the longest items (stepwise kernel; scheduled launches of a configuration
+// with split items): the launch after the measuring one records their sample-start RNG states,
+// later launches with the same seed run each of their samples as a separate work item.
+// L.split_mode, the buffers of the split samples and, for a replay, its claim order.
+int split_samples(rt_ctx* c, Launch& L, int mask, RenderParams& P) {
+  const rt_render_args* a = L.a;
+  // (split samples: the stepwise kernel, and render_kernel's parking variants)
+  const bool split_ok = L.have_perm && c->n_split > 0 && a->spp > 1 && (a->flags & RT_FLAG_NO_SPLIT) == 0 &&
+                        ((mask & F_STEP) != 0 || parks_segment_mask(mask));
+  if (!split_ok) return RT_OK;
+  int split_mode = c->split_state == 1 && c->split_seed == a->seed ? 2 : 1;
+  const long long need = (long long)c->n_split * a->spp;
+  bool moved = false;
+  int rc = reserve(c, c->ckpt, 2 * need, "split sample states", &moved);
+  if (moved) {  // nothing recorded any more: this launch records
+    c->split_state = -1;
+    split_mode = 1;
+  }
+  if (rc) return rc;
+  if (split_mode == 2 && (rc = reserve(c, c->contrib, 3 * need, "split sample contributions"))) return rc;
+  // REF camera state at every sample start
+  if ((rc = camera_samples(c, a, c->cam_st_key, c->cam_st, c->cam_st_host, "camera states"))) return rc;
+  // Split launches claim split samples and unsplit items in one sequence, longest first by the
+  // recording launch's counts (the long samples of a small share start with the launch instead of
+  // trailing it).  Built once per recording; results do not depend on the order.
+  const long long rest = L.items - (long long)c->n_split;
+  if (split_mode == 2 && c->rest_n == rest && c->opt.split_order != 0) {  // 0: samples in item order, then the rest
+    if (!c->order_ok) {
+      if ((rc = reserve(c, c->order, need + rest, "claim order"))) return rc;
+      uint8_t* len = sort_keys(c, need);
+      if (!len) return fail(c, RT_ERR_HIP, "out of device memory (split order)");
+      split_len_kernel<<<(unsigned)((need + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
+          c->ckpt.get(), (unsigned long long)need, a->spp, len);
+      HIPCHK(c, hipGetLastError());
+      unsigned hist[256];
+      if ((rc = sort_hist(c, need, hist))) return rc;
+      std::vector<unsigned>& t = c->order_tab_host;
+      t.assign(256 + 2 * kOrderKeys, 0u);
+      unsigned* sub_base = t.data();
+      unsigned* sub_ge = t.data() + 256;
+      unsigned* rest_gt = t.data() + 256 + kOrderKeys;
+      for (int v = 255; v >= 0; --v) sub_ge[v] = sub_ge[v + 1] + hist[v];  // sub_ge[256] = 0
+      for (int v = 0; v < 256; ++v) sub_base[v] = c->rest_gt[(size_t)v] + sub_ge[v + 1];
+      std::copy(c->rest_gt.begin(), c->rest_gt.end(), rest_gt);
+      HIPCHK(c, hipMemcpyAsync(c->order_tab.get(), t.data(), t.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+      if ((rc = sort_scatter(c, need, c->order_tab.get(), c->order.get()))) return rc;
+      if (rest > 0) {
+        order_rest_kernel<<<(unsigned)((rest + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
+            (unsigned long long)need, (unsigned long long)rest, c->order_tab.get(), c->order.get());
+        HIPCHK(c, hipGetLastError());
+      }
+      c->order_ok = true;
+    }
+    P.order = c->order.get();
+  }
+  L.split_mode = P.split_mode = split_mode;
+  P.n_split = c->n_split;
+  P.ckpt = c->ckpt.get();
+  P.contrib = c->contrib.get();
+  P.cam_st = c->cam_st.get();
+  if (split_mode == 2) P.total_items = (unsigned long long)need + (unsigned long long)rest;
+  return RT_OK;
+}
+// The tile buffer holds what `key` names: `words` of room and build's kernel queued when it held another.
+template <class Build>
+int tile_table(rt_ctx* c, const Key<3>& key, long long words, Build build) {
+  if (key == c->tiles_key) return RT_OK;
+  c->tiles_key.invalidate();
+  if (int rc = reserve(c, c->tiles, words, "camera tiles")) return rc;
+  build();
+  HIPCHK(c, hipGetLastError());
+  c->tiles_key = key;
+  return RT_OK;
+}
+// Camera-ray culling, built once per (scene, W, H): candidate lists for the stepwise kernel
+// (world = one BVH), top-level entry masks for list worlds.  Not in the exact / audit modes,
+// whose counters are the reference's.
+int camera_culling(rt_ctx* c, const rt_render_args* a, const KernelChoice& K, RenderParams& P) {
+  if ((a->flags & RT_FLAG_NO_CAMERA_BINS) != 0 || (K.mask & (F_EXACT | F_CHECK)) != 0) return RT_OK;
+  const int tx = (a->width + (1 << kTileShift) - 1) >> kTileShift, ty = (a->height + (1 << kTileShift) - 1) >> kTileShift;
+  const long long nt = (long long)tx * ty, ntp = (nt + 3) & ~3LL;  // tile lists: counts, then entries from ntp
+  const unsigned grid = (unsigned)((nt + kBlock - 1) / kBlock);
+  // Camera-ray candidate lists pay when lanes get many items each; for a small share (a rank of a
+  // multi-GPU image) the launch ends with its longest items and the lists made that tail longer
+  // (C2, one GPU rendering each rank's share: N = 4 (9.2 items per resident lane) 5.24 ms with
+  // lists vs 5.94 without, N = 8 (4.6 per lane) 4.03 vs 3.51 ms).
+  const double bins_min = c->opt.bins_min_items_per_lane;  // items per resident lane (default 6)
+  if ((K.mask & F_STEP) == 0 && c->bin_n < 0) {
+    // (masks, not lists: a height no list key has)
+    const Key<3> key = {c->scene_gen, a->width, -1 - (long long)a->height};
+    if (int rc = tile_table(c, key, nt, [&] {
+          bin_masks_kernel<<<grid, kBlock, 0, c->stream>>>(c->bin_sph, -c->bin_n, c->scene.cam, a->width, a->height, tx, ty,
+                                                           (uint32_t*)c->tiles.get());
+        }))
+      return rc;
+    P.tile_mask = (const uint32_t*)c->tiles.get();
+    P.tiles_x = tx;
+  } else if ((K.mask & F_STEP) != 0 && c->bin_n > 0 && (double)P.total_items >= bins_min * K.lanes) {
+    const Key<3> key = {c->scene_gen, a->width, a->height};
+    if (int rc = tile_table(c, key, ntp + nt * kTileCap * 2, [&] {
+          bin_tiles_kernel<<<grid, kBlock, 0, c->stream>>>(c->bin_sph, c->bin_ids, c->bin_n, c->scene.cam, a->width, a->height,
+                                                           tx, ty, c->tiles.get(), c->tiles.get() + ntp);
+        }))
+      return rc;
+    P.tile_cnt = c->tiles.get();
+    P.tile_ent = c->tiles.get() + ntp;  // 16-byte aligned: tile_candidates reads int4 groups
+    P.tiles_x = tx;
+    P.tile_cap = kTileCap;
+  }
+  return RT_OK;
+}
+// The first launch of a configuration has no measured item costs; a probe launch estimates them:
+// sample 0 of the first fb (the item's own first sample: same state, same camera draw) at every
+// ps-th owned row position and pixel, into the frame buffer's first fb slice, which the launch then
+// overwrites.  An item's estimate is the mean count of the grid points within kProbeRadius of its
+// own (rows and pixels) times spp; the launch claims items longest first by it (and records the
+// real counts, from which the next launch builds the schedule).  Inside the timed region: the
+// probe is part of the draw.  Grid step (options.probe_schedule < 0, the default): the smallest
+// with step^2 * spp * fb_count >= 200, a probe of at most ~0.5 % of the draw's samples.  Measured
+// (MI355X, cold first launches, no probe -> probe): whole frames C4 77.3 -> 67.0 ms (step 1; 4:
+// 69.6), C5 67.8 -> 64.0 (step 4; 2: 65.1, 8: 64.8), C2 17.02 -> 16.96 (step 4; 1: 17.28); not for
+// scenes without BVHs: C3's list of rects and media lost at every share size (N = 1 / 2 / 4 / 8
+// 14.73 / 8.10 / 4.93 / 3.23 -> 15.64 / 8.94 / 5.70 / 4.04 ms), its costs short and spatially
+// random, the natural order's coherence better (profiles/r05/probe/).
+// This stage, before the timed region: whether the launch probes (L.probe), its grid and room for its counts.
+int probe_grid(rt_ctx* c, Launch& L, const KernelChoice& K) {
+  const rt_render_args* a = L.a;
   int ps = c->opt.probe_schedule;  // probe grid step (0: no probe)
   if (ps < 0)
     for (ps = 1; ps < 64 && (long long)ps * ps * a->spp * a->fb_count < 200; ++ps) {
     }
-  const bool probe = sched && !have_perm && ps > 0 && !check && (long long)a->spp * a->fb_count >= 4 &&
-                     (vmask & (F_STEP | F_BVH)) != 0 && items <= c->item_cap &&
-                     (c->opt.probe_max_items_per_lane <= 0.0f ||
-                      (double)items < (double)c->opt.probe_max_items_per_lane * lanes);
-  const int prow = (rows + ps - 1) / std::max(1, ps), pw = (a->width + ps - 1) / std::max(1, ps);
-  const long long pitems = (long long)prow * pw;
-  if (probe && pitems > c->probe_cap) {  // raw counts, then the smoothed grid
-    if (c->probe_cost) HIPCHK(c, hipFree(c->probe_cost));
-    c->probe_cost = nullptr;
-    c->probe_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->probe_cost, 2 * (size_t)pitems * sizeof(uint16_t)));
-    c->probe_cap = pitems;
-  }
-  HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-  if (probe) {
-    RenderParams Q = P;
-    Q.spp = 1;
-    Q.fb_count = 1;
-    // a probe sample's path is cut after probe_depth segments: the launch (one sample per lane) lasts as
-    // long as its longest path, and the estimate needs only the short ones' counts to rank regions.
-    // Automatic (-1): 10 for the stepwise kernel, 20 for render_kernel.  Measured (MI355X, one GPU
-    // rendering every rank's share, first launches, ms at N = 1 / 4 / 8; profiles/r06/probe_depth/):
-    // C2 full depth 16.94 / 5.66 / 4.08, 10: 16.71 / 5.68 / 3.97, 6: 16.68 / 5.69 / 4.25; C4 full
-    // 66.25 / 26.55 / 25.71, 10: 65.61 / 25.25 / 24.34, 16: 65.42 / 25.77 / 25.19; C5 full 64.26 /
-    // 22.65 / 15.36, 10: 63.65 / 22.24 / 16.19, 20: 63.12 / 21.86 / 14.96
-    const int pd = c->opt.probe_depth >= 0 ? c->opt.probe_depth : ((vmask & F_STEP) != 0 ? 10 : 20);
-    if (pd > 0) Q.max_depth = std::min(a->max_depth, pd);
-    Q.total_items = (unsigned long long)pitems;
-    Q.pstep = ps;
-    Q.per_row = pw;
-    Q.perm = nullptr;
-    Q.n_long = 0;
-    Q.item_cost = c->probe_cost;
-    Q.row_cost = nullptr;
-    Q.split_mode = 0;
-    void* qargs[] = {&Q};
-    HIPCHK(c, hipLaunchKernel(kVariants[probe_variant(var)].fn, dim3(blocks), dim3(bs), qargs, shmem, c->stream));
-    HIPCHK(c, hipGetLastError());
-    RT_DIAG_PROBE_COSTS(c, pitems);  // diagnostic builds only (rt_diag.h): the raw probe counts to a file
-    probe_smooth_kernel<<<(unsigned)((pitems + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
-        c->probe_cost, c->probe_cost + pitems, prow, pw);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemsetAsync(c->work, 0, 8 * sizeof(unsigned long long), c->stream));
-    // The probe's schedule overwrites the context's one (perm, long prefix, split items): whatever
-    // configuration perm_key named no longer has its schedule, so it runs cold again when it repeats
-    // (A, A, probe of B, A must not claim A's items through B's perm).
-    std::fill(c->perm_key, c->perm_key + K, -1LL);
-    c->split_state = -1;
-    c->n_split = 0;
-    c->order_ok = false;
-    // spread head (automatic: the stepwise triangle-mesh variants, every position of the first claims
-    // strided).  Measured (MI355X, one GPU rendering each rank's share, first launches, ms at N = 1 / 2 /
-    // 4 / 8; profiles/r06/spread/): C4 in order 65.54 / 36.87 / 24.42 / 24.20, spread 1 65.53 / 36.79 /
-    // 24.61 / 23.93, 8 65.45 / 36.92 / 24.43 / 19.10, 64 65.56 / 36.89 / 24.64 / 18.33; C2 in order 16.77 /
-    // 9.06 / 5.76 / 3.96, 1 16.74 / 9.09 / 5.46 / 3.99, 64 16.89 / 9.26 / 5.89 / 4.44 (its waves lose the
-    // coherence of neighbouring items)
-    const int spread_top =
-        c->opt.spread_first >= 0 ? c->opt.spread_first : (step_kernel && (vmask & F_TRI) != 0 ? 64 : 0);
-    if ((rc = probe_schedule(c, items, a->spp, a->width, a->fb_count, ps, pw, pitems, step_kernel,
-                             (long long)blocks * (bs / 64), spread_top)))
-      return rc;
-    P.perm = c->perm;
-    P.n_long = c->n_long;
-  }
+  L.probe = L.sched && !L.have_perm && ps > 0 && (a->flags & RT_FLAG_AUDIT) == 0 && (long long)a->spp * a->fb_count >= 4 &&
+            (K.mask & (F_STEP | F_BVH)) != 0 && L.items <= item_cap(c) &&
+            (c->opt.probe_max_items_per_lane <= 0.0f ||
+             (double)L.items < (double)c->opt.probe_max_items_per_lane * K.lanes);
+  L.ps = ps;
+  L.prow = (L.rows + ps - 1) / std::max(1, ps);
+  L.pw = (a->width + ps - 1) / std::max(1, ps);
+  L.pitems = (long long)L.prow * L.pw;
+  // raw counts, then the smoothed grid
+  return L.probe ? reserve(c, c->probe_cost, 2 * L.pitems, "probe counts") : RT_OK;
+}
+// The probe launch and the schedule built from it, inside the timed region: P.perm, P.n_long.
+int probe_launch(rt_ctx* c, const Launch& L, const KernelChoice& K, RenderParams& P) {
+  const rt_render_args* a = L.a;
+  RenderParams Q = P;
+  Q.spp = 1;
+  Q.fb_count = 1;
+  // a probe sample's path is cut after probe_depth segments: the launch (one sample per lane) lasts as
+  // long as its longest path, and the estimate needs only the short ones' counts to rank regions.
+  // Automatic (-1): 10 for the stepwise kernel, 20 for render_kernel.  Measured (MI355X, one GPU
+  // rendering every rank's share, first launches, ms at N = 1 / 4 / 8; profiles/r06/probe_depth/):
+  // C2 full depth 16.94 / 5.66 / 4.08, 10: 16.71 / 5.68 / 3.97, 6: 16.68 / 5.69 / 4.25; C4 full
+  // 66.25 / 26.55 / 25.71, 10: 65.61 / 25.25 / 24.34, 16: 65.42 / 25.77 / 25.19; C5 full 64.26 /
+  // 22.65 / 15.36, 10: 63.65 / 22.24 / 16.19, 20: 63.12 / 21.86 / 14.96
+  const int pd = c->opt.probe_depth >= 0 ? c->opt.probe_depth : ((K.mask & F_STEP) != 0 ? 10 : 20);
+  if (pd > 0) Q.max_depth = std::min(a->max_depth, pd);
+  Q.total_items = (unsigned long long)L.pitems;
+  Q.pstep = L.ps;
+  Q.per_row = L.pw;
+  Q.perm = nullptr;
+  Q.n_long = 0;
+  Q.item_cost = c->probe_cost.get();
+  Q.row_cost = nullptr;
+  Q.split_mode = 0;
+  void* qargs[] = {&Q};
+  HIPCHK(c, hipLaunchKernel(kVariants[probe_variant(K.var)].fn, dim3(K.blocks), dim3(K.bs), qargs, K.shmem, c->stream));
+  HIPCHK(c, hipGetLastError());
+  RT_DIAG_PROBE_COSTS(c, L.pitems);  // diagnostic builds only (rt_diag.h): the raw probe counts to a file
+  probe_smooth_kernel<<<(unsigned)((L.pitems + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
+      c->probe_cost.get(), c->probe_cost.get() + L.pitems, L.prow, L.pw);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemsetAsync(c->work.get(), 0, 8 * sizeof(unsigned long long), c->stream));
+  // The probe's schedule overwrites the context's one (perm, long prefix, split items): whatever
+  // configuration perm_key named no longer has its schedule, so it runs cold again when it repeats
+  // (A, A, probe of B, A must not claim A's items through B's perm).
+  drop_schedule(c);
+  // spread head (automatic: the stepwise triangle-mesh variants, every position of the first claims
+  // strided).  Measured (MI355X, one GPU rendering each rank's share, first launches, ms at N = 1 / 2 /
+  // 4 / 8; profiles/r06/spread/): C4 in order 65.54 / 36.87 / 24.42 / 24.20, spread 1 65.53 / 36.79 /
+  // 24.61 / 23.93, 8 65.45 / 36.92 / 24.43 / 19.10, 64 65.56 / 36.89 / 24.64 / 18.33; C2 in order 16.77 /
+  // 9.06 / 5.76 / 3.96, 1 16.74 / 9.09 / 5.46 / 3.99, 64 16.89 / 9.26 / 5.89 / 4.44 (its waves lose the
+  // coherence of neighbouring items)
+  const int spread_top =
+      c->opt.spread_first >= 0 ? c->opt.spread_first : (L.step_kernel && (K.mask & F_TRI) != 0 ? 64 : 0);
+  if (int rc = probe_schedule(c, L.items, a->spp, a->width, a->fb_count, L.ps, L.pw, L.pitems, L.step_kernel,
+                              (long long)K.blocks * (K.bs / 64), spread_top))
+    return rc;
+  P.perm = c->perm.get();
+  P.n_long = c->n_long;
+  return RT_OK;
+}
+// The render launch (and the split merge), its read-back, and what the context records of it.
+int launch_and_record(rt_ctx* c, const Launch& L, const KernelChoice& K, RenderParams& P, rt_counters* counters) {
+  const rt_render_args* a = L.a;
   RT_STEP_COUNT_HOST_RESET();
   RT_STAMP_HOST_RESET();
   RT_WAVE_HOST_RESET();
   void* kargs[] = {&P};
   // rt_last_kernel_ms: the render kernel (and the split merge), not the probe before it
   HIPCHK(c, hipEventRecord(c->ev2, c->stream));
-  HIPCHK(c, hipLaunchKernel(kVariants[var].fn, dim3(blocks), dim3(bs), kargs, shmem, c->stream));
+  HIPCHK(c, hipLaunchKernel(kVariants[K.var].fn, dim3(K.blocks), dim3(K.bs), kargs, K.shmem, c->stream));
   HIPCHK(c, hipGetLastError());
-  if (split_mode == 2) {
+  if (L.split_mode == 2) {
     merge_split_kernel<<<(unsigned)((c->n_split + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(P);
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-  c->last_sched = (have_perm ? RT_SCHED_PREVIOUS : 0) | (split_mode == 2 ? RT_SCHED_SPLIT_REPLAY : 0) |
-                  (probe ? RT_SCHED_PROBE : 0);
+  c->last_sched = (L.have_perm ? RT_SCHED_PREVIOUS : 0) | (L.split_mode == 2 ? RT_SCHED_SPLIT_REPLAY : 0) |
+                  (L.probe ? RT_SCHED_PROBE : 0);
   snprintf(c->last_kernel, sizeof(c->last_kernel), "%s<%d>",
-           (kVariants[var].mask & F_STEP) != 0 ? "render_step_kernel" : "render_kernel", kVariants[var].mask);
+           (K.mask & F_STEP) != 0 ? "render_step_kernel" : "render_kernel", K.mask);
   unsigned long long host_cnt[8];
-  HIPCHK(c, hipMemcpyAsync(host_cnt, c->work, sizeof(host_cnt), hipMemcpyDeviceToHost, c->stream));
-  std::vector<unsigned long long> cost(measure_rows ? (size_t)a->height : 0);
-  if (measure_rows)
-    HIPCHK(c, hipMemcpyAsync(cost.data(), c->row_cost, cost.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+  HIPCHK(c, hipMemcpyAsync(host_cnt, c->work.get(), sizeof(host_cnt), hipMemcpyDeviceToHost, c->stream));
+  std::vector<unsigned long long> cost(L.measure_rows ? (size_t)a->height : 0);
+  if (L.measure_rows)
+    HIPCHK(c, hipMemcpyAsync(cost.data(), c->row_cost.get(), cost.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                              c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (measure_rows) {
+  if (L.measure_rows) {
     c->host_cost.assign((size_t)a->height, 0ull);
-    std::copy(key, key + 5, c->cost_key);
-    for (int q = 0; q < rows; ++q) c->host_cost[rm[q]] = cost[rm[q]];
+    c->cost_key = L.cost_key;
+    for (int q = 0; q < L.rows; ++q) c->host_cost[L.rm[q]] = cost[L.rm[q]];
   }
-  if (sched && !have_perm) {  // the schedule is built from these counts when the configuration repeats
-    std::copy(pkey, pkey + K, c->pending_key);
+  if (L.sched && !L.have_perm) {  // the schedule is built from these counts when the configuration repeats
+    c->pending_key = L.pkey;
     c->pending_segs = host_cnt[1];
   }
-  if (split_mode == 1) {  // sample-start states recorded for this seed
+  if (L.split_mode == 1) {  // sample-start states recorded for this seed
     c->split_state = 1;
     c->order_ok = false;
     c->split_seed = a->seed;
@@ -5055,12 +5030,47 @@ int rtctx::render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_coun
     counters->fallbacks = host_cnt[5];
   }
   RT_WAVE_HOST_WRITE();
-  RT_STEP_COUNT_HOST_PRINT(var);
+  RT_STEP_COUNT_HOST_PRINT(K.var);
   RT_STAMP_HOST_WRITE();
   // (split samples: items != work items)
-  if (host_cnt[4] != (unsigned long long)a->spp * (tl ? tl->n_items : (unsigned long long)items))
+  if (host_cnt[4] != (unsigned long long)a->spp * (L.tl ? L.tl->n_items : (unsigned long long)L.items))
     return fail(c, RT_ERR_HIP, "render kernel did not complete every sample");
   return RT_OK;
+}
+
+}  // namespace
+
+// tl (a tile launch): the launch claims tl's items in tl's order and is isolated from the context's
+// schedule state -- no schedule is read, built or recorded (perm_key, pending_key, the split state and
+// host_cost / cost_key stay as they are; the schedule flags have no effect), no probe, no split samples,
+// n_long = 0, no item or row costs, rows in ascending order (the row-map cache is kept up to date).
+int rtctx::render_dev(rt_ctx* c, const rt_render_args* a, float* fb_dev, rt_counters* counters, const TileLaunch* tl) {
+  if (!c->have_scene) return fail(c, RT_ERR_STATE, "no scene uploaded");
+  if (!states_are(c, a->width, a->height, a->seed)) return fail(c, RT_ERR_STATE, "rt_render_init not called for this size/seed");
+  if (!fb_dev) return fail(c, RT_ERR_ARG, "null fb");
+  HIPCHK(c, hipSetDevice(c->device));
+  Launch L(a, tl);
+  L.rows = rt_owned_rows(a, nullptr);
+  if (L.rows <= 0) return fail(c, RT_ERR_ARG, "no rows owned");
+  L.items = (long long)a->fb_count * L.rows * a->width;
+  L.step_kernel = (c->world_step || c->world_tree) && (a->flags & (RT_FLAG_NO_STEP | RT_FLAG_WIDEST)) == 0;
+  // (up to 2^31 items: 6 bytes of cost and position per item, C5's configured 100 fb x 100 spp draw
+  // has 829 M; perm holds 32-bit positions)
+  L.sched = !tl && L.items <= (1LL << 31) && (a->flags & RT_FLAG_NO_SCHEDULE) == 0;
+  // cam_mode is part of the key: the split samples' recorded sample-start states depend on it (the
+  // PER_PIXEL camera draws come from the pixel's own state, REF ones from the slot-0 copy)
+  L.pkey = {c->scene_gen, a->width,   a->height,    a->spp,       a->max_depth, a->fb_first,
+            a->fb_count,  a->band_rows, a->band_first, a->band_stride, a->cam_mode};
+  RenderParams P{};
+  KernelChoice K;
+  int rc;
+  if ((rc = row_tables(c, L)) || (rc = schedule_state(c, L)) || (rc = render_params(c, L, fb_dev, P)) ||
+      (rc = pick_kernel(c, L, P, K)) || (rc = split_samples(c, L, K.mask, P)) || (rc = camera_culling(c, a, K, P)) ||
+      (rc = probe_grid(c, L, K)))
+    return rc;
+  HIPCHK(c, hipEventRecord(c->ev0, c->stream));  // the timed region: probe, schedule, render kernel, merge
+  if (L.probe && (rc = probe_launch(c, L, K, P))) return rc;
+  return launch_and_record(c, L, K, P, counters);
 }
 
 extern "C" {
@@ -5075,7 +5085,7 @@ int rt_read_states(rt_ctx* c, int64_t first, int64_t count, uint32_t* out) {
   if (!c->states || first + count > c->states_n) return fail(c, RT_ERR_STATE, "states not initialised");
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<uint4> tmp((size_t)count * 2);
-  HIPCHK(c, hipMemcpyAsync(tmp.data(), c->states + 2 * first, tmp.size() * sizeof(uint4), hipMemcpyDeviceToHost,
+  HIPCHK(c, hipMemcpyAsync(tmp.data(), c->states.get() + 2 * first, tmp.size() * sizeof(uint4), hipMemcpyDeviceToHost,
                            c->stream));  // after rt_render_init's kernel on the same stream
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int64_t k = 0; k < count; ++k) {
@@ -5091,9 +5101,9 @@ int rt_audit_log(rt_ctx* c, float* out, int32_t cap) {
   if (!c->dbg) return 0;
   if (hipSetDevice(c->device) != hipSuccess) return -1;
   unsigned n = 0;
-  if (hipMemcpy(&n, c->dbg, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (hipMemcpy(&n, c->dbg.get(), 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   const int m = (int)std::min<unsigned>(n, (unsigned)std::min(cap, kAuditCap));
-  if (out && m > 0 && hipMemcpy(out, c->dbg + 16, (size_t)m * 16 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+  if (out && m > 0 && hipMemcpy(out, c->dbg.get() + 16, (size_t)m * 16 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
     return -1;
   return (int)n;
 }
@@ -5107,26 +5117,20 @@ int rt_resolve(rt_ctx* c, const rt_render_args* a, const float* fb, uint8_t* out
   const long long per_fb = (long long)rt_owned_rows(a, nullptr) * a->width * 3;
   const long long blocks = (per_fb + kBlock - 1) / kBlock;
   // host buffers (either side) are staged through device memory
-  const bool fb_host = !device_ptr(fb), out_host = !device_ptr(out);
-  float* fb_tmp = nullptr;
-  uint8_t* out_tmp = nullptr;
-  if (fb_host) {
-    HIPCHK(c, hipMalloc((void**)&fb_tmp, (size_t)per_fb * a->fb_count * sizeof(float)));
-    if (hipMemcpy(fb_tmp, fb, (size_t)per_fb * a->fb_count * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-      rc = fail(c, RT_ERR_HIP, "copy frame buffer to device");
-  }
-  if (!rc && out_host && hipMalloc((void**)&out_tmp, (size_t)per_fb) != hipSuccess) rc = fail(c, RT_ERR_NOMEM, "hipMalloc out");
-  if (!rc) {
-    hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, c->stream, fb_host ? fb_tmp : fb,
-                       out_host ? out_tmp : out, per_fb, a->fb_count);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
-      rc = fail(c, RT_ERR_HIP, "resolve kernel");
-  }
-  if (!rc && out_host && hipMemcpy(out, out_tmp, (size_t)per_fb, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(c, RT_ERR_HIP, "copy image to host");
-  if (fb_tmp) (void)hipFree(fb_tmp);
-  if (out_tmp) (void)hipFree(out_tmp);
-  return rc;
+  const size_t n_fb = (size_t)per_fb * a->fb_count;
+  const Staged<float> sfb(fb, n_fb);
+  if (!sfb.ok()) return fail(c, RT_ERR_HIP, "out of device memory (frame buffer)");
+  if (sfb.host() && hipMemcpy(sfb.dev(), fb, n_fb * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(c, RT_ERR_HIP, "copy frame buffer to device");
+  const Staged<uint8_t> sout(out, (size_t)per_fb);
+  if (!sout.ok()) return fail(c, RT_ERR_NOMEM, "hipMalloc out");
+  hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, c->stream, sfb.dev(), sout.dev(), per_fb,
+                     a->fb_count);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+    return fail(c, RT_ERR_HIP, "resolve kernel");
+  if (sout.host() && hipMemcpy(out, sout.dev(), (size_t)per_fb, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(c, RT_ERR_HIP, "copy image to host");
+  return RT_OK;
 }
 
 int rt_draw(rt_ctx* c, const rt_render_args* a, uint8_t* png_rgb_host, rt_counters* counters) {
@@ -5139,20 +5143,15 @@ int rt_draw(rt_ctx* c, const rt_render_args* a, uint8_t* png_rgb_host, rt_counte
   if (rc) return rc;
   if ((rc = rt_render_init(c, a->width, a->height, a->seed))) return rc;
   const size_t npx = (size_t)a->width * a->height;
-  float* fb = nullptr;
-  uint8_t* img = nullptr;
-  HIPCHK(c, hipMalloc((void**)&fb, npx * 3 * sizeof(float) * a->fb_count));
-  if (hipMalloc((void**)&img, npx * 3) != hipSuccess) {
-    (void)hipFree(fb);
-    return fail(c, RT_ERR_NOMEM, "hipMalloc image");
-  }
-  rc = rt_render(c, &full, fb, counters);
-  if (!rc) rc = rt_resolve(c, &full, fb, img);
+  DevBuf<float> fb;
+  DevBuf<uint8_t> img;
+  if (!fb.alloc(npx * 3 * a->fb_count)) return fail(c, RT_ERR_HIP, "out of device memory (frame buffers)");
+  if (!img.alloc(npx * 3)) return fail(c, RT_ERR_NOMEM, "hipMalloc image");
+  rc = rt_render(c, &full, fb.get(), counters);
+  if (!rc) rc = rt_resolve(c, &full, fb.get(), img.get());
   std::vector<uint8_t> tmp(npx * 3);
-  if (!rc && hipMemcpy(tmp.data(), img, tmp.size(), hipMemcpyDeviceToHost) != hipSuccess)
+  if (!rc && hipMemcpy(tmp.data(), img.get(), tmp.size(), hipMemcpyDeviceToHost) != hipSuccess)
     rc = fail(c, RT_ERR_HIP, "copy image");
-  (void)hipFree(fb);
-  (void)hipFree(img);
   if (rc) return rc;
   const size_t row = (size_t)a->width * 3;
   for (int j = 0; j < a->height; ++j) memcpy(png_rgb_host + (size_t)(a->height - 1 - j) * row, tmp.data() + j * row, row);

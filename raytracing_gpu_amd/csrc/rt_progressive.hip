@@ -2,7 +2,7 @@
 // (rt_accum), its noise monitor (rt_noise), launches over a set of noise tiles (rt_render_tiles) and the
 // adaptive accumulator (rt_adapt) of include/rt_hip.h, kernels and host code.  It reaches the render side
 // (rt_kernels.hip) through rt_ctx_internal.h and the public rt_render / rt_render_init only; no device
-// code is called across the two files.
+// code is called across the two files.  Both own their device memory through rt_devbuf.h (DevBuf, Staged).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +15,7 @@
 #include "../../include/rt_hip.h"
 #include "rt_accum_blob.h"
 #include "rt_ctx_internal.h"
+#include "rt_devbuf.h"
 #include "rt_quant.h"
 #include "rt_tile_list.h"
 
@@ -333,60 +334,6 @@ using namespace rtctx;
 
 bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 hipStream_t stream_of(const rt_ctx* c) { return view(c).stream; }
-
-// Device memory of n elements, owned: freed with the object (its device must be current then, as in
-// every rt_*_destroy and wherever a temporary one lives).
-template <class T>
-class DevBuf {
- public:
-  DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
-  DevBuf& operator=(DevBuf&& o) noexcept {
-    std::swap(p_, o.p_);
-    std::swap(n_, o.n_);
-    return *this;
-  }
-  ~DevBuf() {
-    if (p_) (void)hipFree(p_);
-  }
-  // false, and the buffer still empty, when the device has no room
-  bool alloc(size_t n) {
-    if (hipMalloc((void**)&p_, n * sizeof(T)) != hipSuccess) {
-      (void)hipGetLastError();
-      p_ = nullptr;
-      return false;
-    }
-    n_ = n;
-    return true;
-  }
-  // every byte 0, queued on stream
-  bool clear(hipStream_t stream) { return hipMemsetAsync(p_, 0, bytes(), stream) == hipSuccess; }
-  T* get() const { return p_; }
-  size_t bytes() const { return n_ * sizeof(T); }
-  explicit operator bool() const { return p_ != nullptr; }
-
- private:
-  T* p_ = nullptr;
-  size_t n_ = 0;
-};
-
-// A caller's pointer as memory the kernels may address: p itself, or for host memory a temporary device
-// buffer of n elements (the copies in and out are the caller's: which are needed differs).
-template <class T>
-class Staged {
- public:
-  Staged(const T* p, size_t n) : dev_(const_cast<T*>(p)) {
-    if (!device_ptr(p)) dev_ = tmp_.alloc(n) ? tmp_.get() : nullptr;
-  }
-  bool ok() const { return dev_ != nullptr; }  // false: no room for the temporary buffer
-  bool host() const { return (bool)tmp_; }
-  T* dev() const { return dev_; }
-  size_t bytes() const { return tmp_.bytes(); }  // of the temporary buffer
-
- private:
-  DevBuf<T> tmp_;
-  T* dev_;
-};
 
 // The device time between two points of a stream.
 class Timer {

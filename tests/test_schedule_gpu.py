@@ -254,3 +254,67 @@ def test_spread_head_bit_exact(rtlib, gpu_ctx, ctx_opts, oracle, scene, spread):
     for f in range(nfb):
         want = ref.render(W, H, spp, f, 50, REF, rows=sub)[0].reshape(H, W, 3)
         assert np.array_equal(_bits(got[f][js]), _bits(want[js])), f"{scene} spread {spread} fb {f}"
+
+
+@pytest.mark.parametrize("cam", [REF, PIX], ids=["ref", "per_pixel"])
+def test_buffers_grow_under_a_live_schedule(rtlib, oracle, cam):
+    """The context's buffers grow in the middle of a schedule's life.  A fresh context (nothing sized
+    by earlier tests) renders big1 as A = 64x36, 2 spp, 2 fb three times (probe-scheduled, scheduled,
+    split samples replayed), then C = 128x72, 4 spp, 2 fb three times -- larger items, rows, probe grid,
+    split samples and, with its spp, camera tables, so every one of those buffers is reallocated while
+    A's schedule is the live one -- then A three times again inside the buffers C left.  Every frame
+    buffer equals the oracle bit for bit, every sample is counted, and the schedule words are those of
+    the commit before the buffers became owned objects (5ec6c6e, its library built by
+    scripts/build_ab.sh and run through RT_HIP_LIB), both camera modes: [4, 1, 3, 4, 1, 3, 4, 1, 3], that
+    is RT_SCHED_PROBE, RT_SCHED_PREVIOUS, RT_SCHED_PREVIOUS | RT_SCHED_SPLIT_REPLAY for each run of three;
+    the first A after C runs cold again, C's probe having taken the schedule."""
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    A, C = (64, 36, 2), (128, 72, 4)
+    nfb = 2
+    want = {cfg: _big1_frames(cfg[0], cfg[1], cfg[2], nfb, cam) for cfg in (A, C)}
+    ctx = rtlib.Context(0)
+    try:
+        ctx.set_options(bins_min_items_per_lane=0.0, split_min_segments=1.0)
+        ctx.upload(rtlib.Scene.builtin("big1"))
+        seen = []
+        for k, cfg in enumerate([A, A, A, C, C, C, A, A, A]):
+            W, H, spp = cfg
+            got, rows, cnt, sched = _launch(rtlib, ctx, W, H, spp, nfb, cam)
+            seen.append(sched)
+            for f in range(nfb):
+                diff = (_bits(got[f]) != _bits(want[cfg][f][rows])).any(axis=2)
+                assert not diff.any(), f"launch {k} {cfg} fb {f}: {int(diff.sum())} pixels differ"
+            assert cnt["samples"] == nfb * H * W * spp, (k, cfg)
+    finally:
+        ctx.close()
+    print("schedule words:", seen)
+    probe, prev, replay = rtlib.RT_SCHED_PROBE, rtlib.RT_SCHED_PREVIOUS, rtlib.RT_SCHED_SPLIT_REPLAY
+    assert seen == [probe, prev, prev | replay] * 3, seen
+
+
+def test_tile_buffer_switches_between_masks_and_lists(rtlib, oracle):
+    """The camera tile buffer holds entry masks for a list world (one word per tile) and candidate
+    lists for a one-BVH world (counts and entries: much larger), under one key.  On a fresh context:
+    cornell (a list of rects and boxes, no BVH) fills it in its small mask form, big1 grows it to the
+    list form, cornell again builds the masks inside the buffer that is now larger than they need.
+    Each frame buffer equals the oracle bit for bit."""
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    W, H, spp = 64, 64, 2
+    ctx = rtlib.Context(0)
+    try:
+        ctx.set_options(bins_min_items_per_lane=0.0)  # camera lists whatever the share's size
+        for k, name in enumerate(["cornell", "big1", "cornell"]):
+            ctx.upload(rtlib.Scene.builtin(name))
+            got, rows, cnt, _ = _launch(rtlib, ctx, W, H, spp, 1, REF)
+            want = oracle.RefScene(name).render(W, H, spp, 0, 50, REF)[0].reshape(H, W, 3)
+            diff = (_bits(got[0]) != _bits(want[rows])).any(axis=2)
+            assert not diff.any(), f"launch {k} ({name}): {int(diff.sum())} pixels differ"
+            assert cnt["samples"] == H * W * spp, (k, name)
+    finally:
+        ctx.close()
