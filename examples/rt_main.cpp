@@ -35,6 +35,11 @@
 //                           tiles of it (Chebyshev) fails (default 0)
 //     --reopen              with --adaptive: on resuming, make the tiles that fail T / M, and those within R
 //                           of one, active again, each from its own count (prints a line with "reopened")
+//     --denoise OUT2.ppm    with --progressive or --adaptive: also write the denoised image of the final state
+//                           (rt_denoise_monitor / rt_denoise_adaptive with the shipped parameters) to OUT2.ppm
+//                           and print a JSON line with "denoised" and "denoise_ms"; needs two frame buffers.
+//                           With --progressive a noise monitor is attached for it (and saved and needed on
+//                           resuming, as with --until-noise) without stopping the draw
 //
 // Writes OUT.ppm (binary P6, top row first) and one JSON line per draw on stdout.  Files written
 // more than once go to a temporary name first and are renamed into place.
@@ -106,9 +111,11 @@ bool read_file(const char* path, std::vector<unsigned char>& out) {
 // draw() through an accumulator: `step` frame buffers at a time, OUT.ppm and the checkpoint
 // rewritten after each step.
 int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int step, const char* ckpt,
-                     const char* out, std::vector<uint8_t>& png, bool until_noise, float noise_t, double noisy_fraction) {
+                     const char* out, std::vector<uint8_t>& png, bool until_noise, float noise_t, double noisy_fraction,
+                     const char* denoised) {
   rt_accum* acc = nullptr;
   rt_noise* mon = nullptr;
+  const bool want_mon = until_noise || denoised;
   const std::string side = std::string(ckpt ? ckpt : "") + ".noise";
   std::vector<unsigned char> blob;
   if (ckpt && read_file(ckpt, blob)) {
@@ -120,16 +127,16 @@ int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int
         b.max_depth != a.max_depth || b.cam_mode != a.cam_mode || b.band_rows != a.band_rows ||
         b.band_first != a.band_first || b.band_stride != a.band_stride || b.seed != a.seed || b.fb_count > a.fb_count)
       return die("checkpoint", "belongs to a draw with other settings");
-    if (until_noise) {  // the statistics cover every frame buffer or the draw does not continue
+    if (want_mon) {  // the statistics cover every frame buffer or the draw does not continue
       std::vector<unsigned char> nb;
-      if (!read_file(side.c_str(), nb)) return die("--until-noise: the checkpoint has no side file", side.c_str());
+      if (!read_file(side.c_str(), nb)) return die("--until-noise / --denoise: the checkpoint has no side file", side.c_str());
       if (rt_noise_load(acc, nb.data(), nb.size(), &mon)) return die("rt_noise_load", rt_last_error(ctx));
     }
     printf("{\"resumed_from\": %d, \"checkpoint\": \"%s\"}\n", b.fb_count, ckpt);
     fflush(stdout);
   } else if (rt_accum_create(ctx, &a, step, &acc)) {
     return die("rt_accum_create", rt_last_error(ctx));
-  } else if (until_noise && rt_noise_create(acc, &mon)) {
+  } else if (want_mon && rt_noise_create(acc, &mon)) {
     return die("rt_noise_create", rt_last_error(ctx));
   }
   char head[64];
@@ -139,7 +146,7 @@ int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int
   const long long pixels = (long long)a.width * a.height;
   auto converged = [&](const rt_noise_report& r) { return r.pixels_above <= (long long)std::floor(noisy_fraction * (double)pixels); };
   bool stop = false;
-  if (mon && i.args.fb_count >= 2) {  // resumed: a draw that had converged stays stopped
+  if (until_noise && i.args.fb_count >= 2) {  // resumed: a draw that had converged stays stopped
     rt_noise_report r = {};
     if (rt_noise_measure(mon, noise_t, &r, nullptr, nullptr)) return die("rt_noise_measure", rt_last_error(ctx));
     stop = converged(r);
@@ -168,7 +175,7 @@ int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int
     }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     rt_noise_report rep = {};
-    const bool measured = mon && i.args.fb_count >= 2;
+    const bool measured = until_noise && i.args.fb_count >= 2;
     if (measured) {
       if (rt_noise_measure(mon, noise_t, &rep, nullptr, nullptr)) return die("rt_noise_measure", rt_last_error(ctx));
       stop = converged(rep);
@@ -185,6 +192,12 @@ int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int
            stop ? "true" : "false", noise_t, noisy_fraction);
     fflush(stdout);
   }
+  if (denoised) {
+    if (rt_denoise_monitor(mon, nullptr, png.data(), nullptr, 1)) return die("rt_denoise_monitor", rt_last_error(ctx));
+    if (!write_file(denoised, head, png.data(), png.size())) return die("write", denoised);
+    printf("{\"denoised\": \"%s\", \"fbs\": %d, \"denoise_ms\": %.3f}\n", denoised, i.args.fb_count, rt_denoise_monitor_last_ms(mon));
+    fflush(stdout);
+  }
   if (mon) rt_noise_destroy(mon);
   rt_accum_destroy(acc);
   return 0;
@@ -194,7 +207,7 @@ int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int
 // beyond NO_FB; with a checkpoint the state is saved after every step and an existing one is continued.
 int draw_adaptive(rt_ctx* ctx, const char* name, const rt_render_args& a, int step, const char* out,
                   std::vector<uint8_t>& png, float noise_t, int max_above, int min_fbs, const char* ckpt, int dilate,
-                  bool reopen) {
+                  bool reopen, const char* denoised) {
   rt_adapt* ad = nullptr;
   rt_adapt_report rep = {};
   int done = 0;
@@ -278,6 +291,12 @@ int draw_adaptive(rt_ctx* ctx, const char* name, const rt_render_args& a, int st
   printf("{\"stopped_at\": %d, \"pixel_fbs\": %lld, \"tiles_active\": %d, \"until_noise\": %.9g, \"max_above\": %d}\n", done,
          pixel_fbs, measured ? rep.tiles_active : -1, noise_t, max_above);
   fflush(stdout);
+  if (denoised) {
+    if (rt_denoise_adaptive(ad, nullptr, png.data(), nullptr, 1)) return die("rt_denoise_adaptive", rt_last_error(ctx));
+    if (!write_file(denoised, head, png.data(), png.size())) return die("write", denoised);
+    printf("{\"denoised\": \"%s\", \"fbs\": %d, \"denoise_ms\": %.3f}\n", denoised, done, rt_denoise_adaptive_last_ms(ad));
+    fflush(stdout);
+  }
   rt_adapt_destroy(ad);
   return 0;
 }
@@ -289,7 +308,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: rt_main SCENE WIDTH SPP_PER_FB NO_FB OUT.ppm [--devices 0,1] [--gather rccl|host] "
                     "[--band-rows B] [--repeat K] [--depth D] [--height H] [--obj PATH] [--tex PATH] [--progressive K] [--checkpoint FILE] "
                     "[--until-noise T [--noisy-fraction F]] [--adaptive K --until-noise T [--max-above M] [--min-fbs F] "
-                    "[--adaptive-checkpoint FILE] [--dilate R] [--reopen]]\n");
+                    "[--adaptive-checkpoint FILE] [--dilate R] [--reopen]] [--denoise OUT2.ppm]\n");
     return 2;
   }
   const char* name = argv[1];
@@ -300,7 +319,7 @@ int main(int argc, char** argv) {
   const char* out = argv[5];
   std::vector<int> devices;
   int gather = RT_GATHER_RCCL, band_rows = 4, repeat = 1;
-  const char *obj_path = nullptr, *tex_path = nullptr, *ckpt_path = nullptr, *adaptive_ckpt = nullptr;
+  const char *obj_path = nullptr, *tex_path = nullptr, *ckpt_path = nullptr, *adaptive_ckpt = nullptr, *denoised = nullptr;
   int dilate = 0;
   bool reopen = false, have_resume_opts = false;
   int height = 0;
@@ -329,6 +348,7 @@ int main(int argc, char** argv) {
     else if (a == "--dilate") have_resume_opts = true, dilate = atoi(v), ++k;
     else if (a == "--reopen") have_resume_opts = true, reopen = true;
     else if (a == "--until-noise") until_noise = true, noise_t = (float)atof(v), ++k;
+    else if (a == "--denoise") denoised = v, ++k;
     else if (a == "--noisy-fraction") have_fraction = true, noisy_fraction = atof(v), ++k;
     else return die("unknown option", argv[k]);
   }
@@ -347,6 +367,8 @@ int main(int argc, char** argv) {
   }
   if (!have_adaptive && (until_noise || have_fraction) && progressive <= 0) return die("--until-noise / --noisy-fraction", "need --progressive K");
   if (have_fraction && !until_noise) return die("--noisy-fraction", "needs --until-noise T");
+  if (denoised && !have_adaptive && progressive <= 0) return die("--denoise", "needs --progressive K or --adaptive K");
+  if (denoised && s.no_fb > 32768) return die("--denoise", "a noise monitor accepts at most 32768 frame buffers");
   if (until_noise && s.no_fb > 32768) return die("--until-noise", "a noise monitor accepts at most 32768 frame buffers");
 
   // ---- scene: the reference's `door_scene curr_scene;` etc. (main.cu:17-18) as the host library
@@ -408,7 +430,7 @@ int main(int argc, char** argv) {
   }
   if (have_adaptive) {
     if (!ctx) return die("--adaptive", "one GPU only (no --devices)");
-    const int rc = draw_adaptive(ctx, name, a, adaptive, out, png, noise_t, max_above, min_fbs, adaptive_ckpt, dilate, reopen);
+    const int rc = draw_adaptive(ctx, name, a, adaptive, out, png, noise_t, max_above, min_fbs, adaptive_ckpt, dilate, reopen, denoised);
     rt_ctx_destroy(ctx);
     rt_scene_free(scene);
     return rc;
@@ -417,7 +439,7 @@ int main(int argc, char** argv) {
     if (!ctx) return die("--progressive / --checkpoint", "one GPU only (no --devices)");
     if (progressive < 0 || a.fb_count < 1) return die("--progressive", "K and NO_FB must be at least 1");
     const int rc = draw_progressive(ctx, name, a, progressive > 0 ? progressive : a.fb_count, ckpt_path, out, png,
-                                      until_noise, noise_t, noisy_fraction);
+                                      until_noise, noise_t, noisy_fraction, denoised);
     rt_ctx_destroy(ctx);
     rt_scene_free(scene);
     return rc;

@@ -615,6 +615,86 @@ int rt_adaptive_blob_measure(const void* blob, size_t n, float threshold, rt_ada
 int rt_adaptive_blob_pack(const rt_accum_info* info, const int32_t* tile_fbs, const uint8_t* active, const float* sums,
                           const uint32_t* s1, const uint64_t* s2, void* blob, size_t cap, size_t* need);
 
+/* ------------------------------------------------------------------ denoiser */
+/* A variance-cancelling non-local-means filter (Rousselle, Knaus, Zwicker 2012) over the moments a noise
+ * monitor or an adaptive accumulator already holds: per value they give the mean of c^2 and the variance of
+ * that mean, which is the input such a filter needs.  Each pixel carries its own n -- the monitor's count, or
+ * n_t of its noise tile for an adaptive accumulator -- so tiles that retired early at a higher noise are
+ * smoothed more.  The calls below change no state: sums, moments, counts and checkpoints stay byte-identical,
+ * and an accumulator that is never denoised launches exactly the kernels it launched before.  (Their names
+ * begin with rt_denoise_ because the rt_noise_, rt_adapt_ and rt_adaptive_ families are closed.)
+ *
+ * The definition is exact: every reduction across pixels is over integers, hence independent of its order,
+ * and every float operation is a single correctly rounded IEEE operation.  No float is summed across pixels
+ * anywhere.  The device kernels and the host-only twin on a checkpoint agree byte for byte.
+ *
+ * The image is rows x width pixels of 3 values, whole-image tiling only (a band tiling is RT_ERR_ARG:
+ * neighbouring owned-row indices are not neighbouring rows).  Pixel p has n = n(p) >= 2 frame buffers
+ * (RT_ERR_STATE otherwise).  Parameters: search_radius R in 0..10, patch_radius f in 0..3, k > 0,
+ * alpha >= 0, eps > 0; anything else (a NaN included) is RT_ERR_ARG.
+ *
+ * Per value j of pixel p, from S1 and S2 as rt_noise defines them:
+ *
+ *   Q = (256 S1 + n / 2) / n                 u64 integer division; Q < 2^24: the mean of c^2, 8 fractional bits
+ *   M = (float)Q / 256.0f                    exact
+ *   D = n S2 - S1^2                          u64
+ *   V = (float)((double)D / ((double)n * (double)n * (double)(n - 1)))    divisor multiplied left to right;
+ *                                            the variance of the mean, in c^2 units
+ *
+ * Distance term of a pair of pixels (a, b) and a channel j, in float, one rounded operation per operator, in
+ * this order:
+ *
+ *   d   = M_a - M_b
+ *   num = d * d - alpha * (V_a + fminf(V_a, V_b))
+ *   den = eps + (k * k) * (V_a + V_b)
+ *   t   = num / den, clamped to [-64, 64]   (a NaN, possible only with k * k = inf, counts as -64)
+ *   T   = (int32)(t * 256.0f)                truncating cast
+ *
+ * For pixel p and search offset o with |o_x|, |o_y| <= R and q = p + o inside the image:
+ *
+ *   P   = sum of T(p + u, q + u, j) over the channels j and the patch offsets u, |u_x|, |u_y| <= f, for which
+ *         both p + u and q + u are inside the image; an int32 sum, |P| <= 147 x 16384, in any order
+ *   cnt = 3 x (number of such u) >= 3
+ *
+ *   x  = (float)P / (float)(256 cnt);   if (x < 0) x = 0
+ *   s  = 1.0f - x * 0.125f;             if (s < 0) s = 0
+ *   s2 = s * s;  s4 = s2 * s2;  s8 = s4 * s4
+ *   W  = (uint32)(s8 * 65536.0f)        (1 - x / 8)^8 stands for e^-x: no transcendental, no libm difference
+ *
+ * The centre offset has P <= 0 and therefore W = 65536, always.  Output per value:
+ *
+ *   Num = sum over o of W Q_q           u64, < 2^49
+ *   Den = sum over o of W               u64, >= 65536
+ *   lin = (float)((double)Num / ((double)Den * 256.0 * 65025.0))          multiplied left to right
+ *   image byte = quant(lin)             write_frame_buffer's quantisation, as every image here
+ *   gain[p] = (float)((double)Den / 65536.0)    how many pixels' worth p was averaged over; 1 where nothing
+ *                                               matched
+ *
+ * The arithmetic of a term and of a weight is stated once, in csrc/rt_denoise_math.h, for both halves. */
+typedef struct rt_denoise_params {
+  int32_t search_radius, patch_radius;
+  float k, alpha, eps;
+  int32_t pad;
+} rt_denoise_params;
+/* The shipped defaults (DESIGN.md 3.7 has the measurements behind them). */
+void rt_denoise_params_default(rt_denoise_params* p);
+/* The denoised image of a monitor's accumulator / of an adaptive accumulator.  out and gain (may be NULL;
+ * [rows][width] floats) follow rt_accum_image's conventions: png_order = 0 is rt_resolve's layout, device or
+ * host pointers; png_order = 1 is rt_draw's, top row first, host pointers.  params = NULL takes the defaults.
+ * Every check comes before anything is written: on an error out and gain are untouched.  Temporary device
+ * memory of 24 bytes per pixel is freed before the call returns. */
+int rt_denoise_monitor(rt_noise* nm, const rt_denoise_params* params, uint8_t* out, float* gain, int32_t png_order);
+int rt_denoise_adaptive(rt_adapt* ad, const rt_denoise_params* params, uint8_t* out, float* gain, int32_t png_order);
+/* Device time in ms of the last denoise (the prepare pass and the filter kernel); 0 before one. */
+float rt_denoise_monitor_last_ms(const rt_noise* nm);
+float rt_denoise_adaptive_last_ms(const rt_adapt* ad);
+/* Host only (no context, no GPU; csrc/rt_denoise_blob.cpp): the same filter on a monitor's side file
+ * (rt_noise_save) or an adaptive checkpoint (rt_adaptive_save); out in rt_resolve's layout, n_values bytes,
+ * gain [rows][width] or NULL, params = NULL for the defaults.  RT_ERR_ARG for a malformed blob, a band tiling,
+ * bad parameters or a null out; RT_ERR_STATE for a pixel with n < 2. */
+int rt_denoise_monitor_blob(const void* blob, size_t n, const rt_denoise_params* params, uint8_t* out, float* gain);
+int rt_denoise_adaptive_blob(const void* blob, size_t n, const rt_denoise_params* params, uint8_t* out, float* gain);
+
 /* ------------------------------------------------------------------ host scene library */
 /* Builds one of the reference scenes (scenes.h) on the host: "basic", "first", "big1" (alias
  * "random"), "two_spheres", "two_perlin", "cornell", "cornell_smoke", "triangle", "triangles",

@@ -171,6 +171,16 @@ class rt_adapt_report(ctypes.Structure):
         return d
 
 
+class rt_denoise_params(ctypes.Structure):
+    """include/rt_hip.h rt_denoise_params."""
+    _fields_ = [("search_radius", c_int32), ("patch_radius", c_int32), ("k", c_float), ("alpha", c_float),
+                ("eps", c_float), ("pad", c_int32)]
+
+    def as_dict(self) -> dict:
+        return {"search_radius": int(self.search_radius), "patch_radius": int(self.patch_radius), "k": float(self.k),
+                "alpha": float(self.alpha), "eps": float(self.eps)}
+
+
 NOISE_MAX_FBS = 32768  # frame buffers a noise monitor accepts (include/rt_hip.h)
 
 # Every entry point of include/rt_hip.h: name -> (restype, argtypes)
@@ -240,6 +250,13 @@ ABI = {
     "rt_adaptive_blob_measure": (c_int, [c_void_p, c_size_t, c_float, POINTER(rt_adapt_report), c_void_p, c_void_p, c_void_p]),
     "rt_adaptive_blob_pack": (c_int, [POINTER(rt_accum_info), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_size_t, POINTER(c_size_t)]),
+    "rt_denoise_params_default": (None, [POINTER(rt_denoise_params)]),
+    "rt_denoise_monitor": (c_int, [c_void_p, POINTER(rt_denoise_params), c_void_p, c_void_p, c_int32]),
+    "rt_denoise_adaptive": (c_int, [c_void_p, POINTER(rt_denoise_params), c_void_p, c_void_p, c_int32]),
+    "rt_denoise_monitor_last_ms": (c_float, [c_void_p]),
+    "rt_denoise_adaptive_last_ms": (c_float, [c_void_p]),
+    "rt_denoise_monitor_blob": (c_int, [c_void_p, c_size_t, POINTER(rt_denoise_params), c_void_p, c_void_p]),
+    "rt_denoise_adaptive_blob": (c_int, [c_void_p, c_size_t, POINTER(rt_denoise_params), c_void_p, c_void_p]),
     "rt_scene_build": (c_int, [c_char_p, POINTER(c_void_p)]),
     "rt_scene_build_ex": (c_int, [c_char_p, c_void_p, POINTER(c_void_p)]),
     "rt_obj_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
@@ -279,6 +296,32 @@ def lib() -> ctypes.CDLL:
 
 
 RT_OK, RT_ERR_ARG, RT_ERR_HIP, RT_ERR_STATE, RT_ERR_SCENE, RT_ERR_NOMEM = range(6)
+
+
+def denoise_params(params=None, **kw) -> rt_denoise_params:
+    """The denoiser's parameters (include/rt_hip.h): the shipped defaults, or a copy of params (an
+    rt_denoise_params, a dict of its fields, True or None for the defaults), with the fields of kw set."""
+    p = rt_denoise_params()
+    if isinstance(params, rt_denoise_params):
+        ctypes.memmove(ctypes.byref(p), ctypes.byref(params), ctypes.sizeof(p))
+    else:
+        lib().rt_denoise_params_default(ctypes.byref(p))
+        if isinstance(params, dict):
+            kw = {**params, **kw}
+    for k, v in kw.items():
+        if k not in ("search_radius", "patch_radius", "k", "alpha", "eps"):
+            raise TypeError(f"rt_denoise_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _denoise_call(check, fn, what, handle, params, rows, width, png_order, gain):
+    """fn(handle, params, image, gain or NULL, png_order) into fresh arrays: image, or (image, gain)."""
+    p = denoise_params(params)
+    img = np.zeros((rows, width, 3), np.uint8)
+    g = np.zeros((rows, width), np.float32) if gain else None
+    check(fn(handle, ctypes.byref(p), img.ctypes.data, g.ctypes.data if gain else None, 1 if png_order else 0), what)
+    return (img, g) if gain else img
 
 
 class RtError(RuntimeError):
@@ -708,6 +751,25 @@ class NoiseMonitor:
         """Device time of the last measure() / map() kernel."""
         return float(lib().rt_noise_last_measure_ms(self._h))
 
+    def denoise(self, params=None, png_order: bool = True, gain: bool = False):
+        """The denoised image of the frame buffers so far (rt_denoise_monitor: a variance-guided NL-means
+        filter on the monitor's moments; needs two frame buffers and the whole-image tiling): (rows, width, 3)
+        uint8, top row first with png_order, and with gain=True also the (rows, width) float32 number of
+        pixels' worth every pixel was averaged over.  params: see denoise_params().  Changes no state."""
+        return _denoise_call(self._check, lib().rt_denoise_monitor, "rt_denoise_monitor", self._h, params, self._rows,
+                             self._width, png_order, gain)
+
+    def denoise_into(self, out_ptr: int, gain_ptr: int = 0, params=None, png_order: bool = False) -> None:
+        """denoise() into caller memory (device addresses with png_order False, or host addresses)."""
+        self.acc.ctx._after_torch()
+        p = denoise_params(params)
+        self._check(lib().rt_denoise_monitor(self._h, ctypes.byref(p), c_void_p(out_ptr), c_void_p(gain_ptr or None),
+                                             1 if png_order else 0), "rt_denoise_monitor")
+
+    def last_denoise_ms(self) -> float:
+        """Device time of the last denoise()'s kernels."""
+        return float(lib().rt_denoise_monitor_last_ms(self._h))
+
     def blob(self) -> bytes:
         need = c_size_t()
         self._check(lib().rt_noise_save(self._h, None, 0, ctypes.byref(need)), "rt_noise_save")
@@ -849,6 +911,16 @@ class AdaptiveAccumulator:
         """Device time of the last retire()'s measure kernel."""
         return float(lib().rt_adapt_last_retire_ms(self._h))
 
+    def denoise(self, params=None, png_order: bool = True, gain: bool = False):
+        """NoiseMonitor.denoise() with every pixel at its own tile's count (rt_denoise_adaptive; every tile
+        needs two frame buffers): tiles that retired early at a higher noise are smoothed more."""
+        return _denoise_call(self.ctx._check, lib().rt_denoise_adaptive, "rt_denoise_adaptive", self._h, params, self._rows,
+                             self._width, png_order, gain)
+
+    def last_denoise_ms(self) -> float:
+        """Device time of the last denoise()'s kernels."""
+        return float(lib().rt_denoise_adaptive_last_ms(self._h))
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             if getattr(self.ctx, "_c", None):
@@ -882,6 +954,35 @@ def read_noise(path: str, threshold: float) -> tuple[dict, np.ndarray, np.ndarra
     if rc != 0:
         raise RtError(f"rt_noise_blob_measure({path!r}) failed ({rc})", rc)
     return {**d, **rep.as_dict()}, tile_max, tile_above, nmap
+
+
+def _denoise_file(path: str, info_fn, fn, what: str, params, gain: bool):
+    with open(path, "rb") as f:
+        blob = f.read()
+    i = rt_accum_info()
+    rc = info_fn(blob, len(blob), ctypes.byref(i))
+    if rc != 0:
+        raise RtError(f"{what}({path!r}): malformed file ({rc})", rc)
+
+    def check(rc, what):
+        if rc != 0:
+            raise RtError(f"{what}({path!r}) failed ({rc})", rc)
+
+    return _denoise_call(check, lambda _, p, img, g, __: fn(blob, len(blob), p, img, g), what, None, params,
+                         i.n_values // (3 * i.args.width), i.args.width, False, gain)
+
+
+def denoise_checkpoint(path: str, params=None, gain: bool = False):
+    """NoiseMonitor.denoise() of a monitor's side file (the checkpoint's ".noise"), by the host-only
+    rt_denoise_monitor_blob (no context, no GPU), byte-identical to the device's: (rows, width, 3) uint8 with
+    rows ascending (bottom row first), and with gain=True the (rows, width) float32 gain too."""
+    return _denoise_file(path, lib().rt_noise_blob_info, lib().rt_denoise_monitor_blob, "rt_denoise_monitor_blob", params, gain)
+
+
+def denoise_adaptive_checkpoint(path: str, params=None, gain: bool = False):
+    """AdaptiveAccumulator.denoise() of an adaptive checkpoint file, by the host-only rt_denoise_adaptive_blob."""
+    return _denoise_file(path, lib().rt_adaptive_blob_info, lib().rt_denoise_adaptive_blob, "rt_denoise_adaptive_blob", params,
+                         gain)
 
 
 def read_checkpoint(path: str) -> tuple[dict, np.ndarray]:
@@ -939,7 +1040,7 @@ def read_adaptive_checkpoint(path: str, threshold: float | None = None) -> tuple
 def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context | None = None, every: int = 1,
                      on_image=None, checkpoint: str | None = None, chunk_fbs: int | None = None,
                      cam_mode: int = RT_CAM_REF_SLOT0, seed: int = 1984, until_noise: float | None = None,
-                     noisy_fraction: float = 0.01, min_fbs: int = 2, on_noise=None) -> tuple[np.ndarray, dict]:
+                     noisy_fraction: float = 0.01, min_fbs: int = 2, on_noise=None, denoise=None) -> tuple[np.ndarray, dict]:
     """draw() of render.h:118-174 in steps of `every` frame buffers: after each step
     on_image(image, fbs_done) gets the PNG-order image so far (the reference leaves tmp/<id>.ppm
     behind, render.h:152-162) and, with a checkpoint path, the state is saved there (temporary name,
@@ -956,20 +1057,26 @@ def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context 
     is saved to checkpoint + ".noise" before the checkpoint itself, and a resumed draw is measured
     before it renders anything (a draw that had converged stays stopped).  Resuming needs that side
     file: a missing one, or one whose header differs from the checkpoint's, raises RtError -- the
-    statistics are never silently restarted from a later frame buffer."""
+    statistics are never silently restarted from a later frame buffer.
+
+    denoise=True (the shipped parameters) or parameters as denoise_params() takes them: a noise monitor is
+    attached if until_noise has not attached one (it never stops the draw then), and the image returned is
+    NoiseMonitor.denoise() of the final state instead of the plain one (needs two frame buffers); on_image
+    still gets the plain images.  None leaves the function exactly as it is without it."""
     if settings.image_height <= 0:
         settings.aspect_ratio = curr_scene.aspect
         settings.calc_all()
     if every < 1:
         raise ValueError("every < 1")
-    if until_noise is not None and settings.no_fb > NOISE_MAX_FBS:
+    want_mon = until_noise is not None or denoise is not None
+    if want_mon and settings.no_fb > NOISE_MAX_FBS:
         raise ValueError(f"a noise monitor accepts at most {NOISE_MAX_FBS} frame buffers")
     own = ctx is None
     ctx = ctx or Context(0)
     acc = mon = None
 
     def converged() -> bool:
-        if mon is None or acc.done < max(2, min_fbs):
+        if until_noise is None or acc.done < max(2, min_fbs):
             return False
         report = mon.measure(until_noise)[0]
         if on_noise is not None:
@@ -987,15 +1094,15 @@ def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context 
             differ = [k for k in want if k not in ("fb_count", "n_values", "scene_fp") and got[k] != want[k]]
             if differ or got["fb_count"] > settings.no_fb:
                 raise RtError(f"checkpoint {checkpoint!r} is of another draw: {differ or 'more frame buffers'}")
-            if until_noise is not None:
+            if want_mon:
                 side = checkpoint + ".noise"
                 if not os.path.exists(side):
                     raise RtError(f"checkpoint {checkpoint!r} has no noise side file {side!r}: the draw cannot "
-                                  "continue with until_noise (the statistics must cover every frame buffer)")
+                                  "continue with until_noise or denoise (the statistics must cover every frame buffer)")
                 mon = NoiseMonitor.load(acc, side)
         else:
             acc = ctx.accumulator(args, chunk)
-            if until_noise is not None:
+            if want_mon:
                 mon = acc.noise_monitor()
         total = rt_counters().as_dict()
         img = acc.image(png_order=True) if acc.done else None
@@ -1011,6 +1118,8 @@ def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context 
             stop = converged()
             if on_image is not None:
                 on_image(img, acc.done)
+        if denoise is not None:
+            img = mon.denoise(denoise)
         return img, total
     finally:
         if acc is not None:
@@ -1023,7 +1132,7 @@ def draw_adaptive(curr_scene: Scene, settings: render_settings, ctx: Context | N
                   until_noise: float = 0.5, max_above: int = 0, min_fbs: int = 4, on_image=None, on_step=None,
                   cam_mode: int = RT_CAM_REF_SLOT0, seed: int = 1984, chunk_fbs: int | None = None,
                   checkpoint: str | None = None, dilate: int = 0,
-                  reopen: bool = False) -> tuple[np.ndarray, dict, np.ndarray]:
+                  reopen: bool = False, denoise=None) -> tuple[np.ndarray, dict, np.ndarray]:
     """draw() that stops rendering a 16 x 16 tile once at most max_above of its pixels have a noise
     estimate above until_noise (8-bit output levels; NoiseMonitor's definition), and goes on with the
     others.  Each step adds `every` frame buffers to the active tiles, none beyond settings.no_fb; from
@@ -1039,7 +1148,11 @@ def draw_adaptive(curr_scene: Scene, settings: render_settings, ctx: Context | N
     stopped; one of another scene, of other settings or with more frame buffers than settings.no_fb raises
     RtError.  reopen=True on a resumed draw first makes the tiles that fail until_noise / max_above (and
     their neighbours within dilate) active again, each from its own count: a finished draw refined to a
-    tighter threshold."""
+    tighter threshold.
+
+    denoise=True (the shipped parameters) or parameters as denoise_params() takes them: the image returned is
+    AdaptiveAccumulator.denoise() of the final state, every pixel at its own tile's count, instead of the plain
+    one (every tile needs two frame buffers); on_image still gets the plain images."""
     if settings.image_height <= 0:
         settings.aspect_ratio = curr_scene.aspect
         settings.calc_all()
@@ -1087,7 +1200,7 @@ def draw_adaptive(curr_scene: Scene, settings: render_settings, ctx: Context | N
             if on_image is not None:
                 on_image(ad.image(png_order=True), done)
         if done:
-            img = ad.image(png_order=True)
+            img = ad.image(png_order=True) if denoise is None else ad.denoise(denoise)
         return img, total, ad.counts()
     finally:
         if ad is not None:

@@ -2,7 +2,8 @@
 // (rt_accum), its noise monitor (rt_noise), launches over a set of noise tiles (rt_render_tiles) and the
 // adaptive accumulator (rt_adapt) of include/rt_hip.h, kernels and host code.  It reaches the render side
 // (rt_kernels.hip) through rt_ctx_internal.h and the public rt_render / rt_render_init only; no device
-// code is called across the two files.  Both own their device memory through rt_devbuf.h (DevBuf, Staged).
+// code is called across the two files.  The denoiser's entry points on rt_noise and rt_adapt are here too; its
+// kernels are rt_denoise.hip's.  Both own their device memory through rt_devbuf.h (DevBuf, Staged).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,8 @@
 #include "../../include/rt_hip.h"
 #include "rt_accum_blob.h"
 #include "rt_ctx_internal.h"
+#include "rt_denoise.h"
+#include "rt_denoise_math.h"
 #include "rt_devbuf.h"
 #include "rt_quant.h"
 #include "rt_tile_list.h"
@@ -507,6 +510,48 @@ int image_out(AccumCore& k, uint8_t* out, int32_t png_order, const char* nomem, 
   return RT_OK;
 }
 
+// rt_denoise_monitor and rt_denoise_adaptive: the checks (every one before anything is written), then
+// rt_denoise.hip's prepare pass and filter over the moments m -- every pixel at n frame buffers, or with
+// tile_n_dev at its noise tile's -- into image_out's image, and the gain beside it under the same conventions.
+// The (M, V) scratch lives for the call only.
+int denoise_out(AccumCore& k, const Moments& m, const int32_t* tile_n_dev, int n, Timer& timer, const rt_denoise_params* params,
+                uint8_t* out, float* gain, int32_t png_order) {
+  rt_ctx* c = k.ctx;
+  rt_denoise_params p;
+  if (params) p = *params;
+  else rt_denoise_params_default(&p);
+  if (!rtdn::params_ok(&p)) return fail(c, RT_ERR_ARG, "denoise: parameters out of range");
+  if (k.per_fb != (long long)k.args.width * k.args.height * 3) return fail(c, RT_ERR_ARG, "denoise needs the whole-image tiling");
+  if (!m.grid.launch_2d_fits()) return fail(c, RT_ERR_ARG, "denoise: too many tiles");
+  HIPCHK(c, hipSetDevice(view(c).device));
+  if (gain && png_order == 1 && device_ptr(gain)) return fail(c, RT_ERR_ARG, "png_order needs a host gain");
+  const size_t pixels = (size_t)m.grid.pixels();
+  DevBuf<float2> mv;
+  DevBuf<float> gain_tmp;  // a host gain is staged through device memory
+  std::vector<float> gain_rows;
+  const bool gain_host = gain && !device_ptr(gain);
+  const int rc = image_out(k, out, png_order, "hipMalloc denoised image", [&](uint8_t* img) {
+    const hipStream_t stream = stream_of(c);
+    if (!mv.alloc(pixels * 3) || (gain_host && !gain_tmp.alloc(pixels))) return fail(c, RT_ERR_NOMEM, "hipMalloc denoise scratch");
+    float* gain_dev = gain_host ? gain_tmp.get() : gain;
+    HIPCHK(c, timer.start(stream));
+    HIPCHK(c, rtdn::launch(stream, m.s1.get(), m.s2.get(), tile_n_dev, n, m.grid.rows, m.grid.width, p, mv.get(), img, gain_dev));
+    HIPCHK(c, timer.stop(stream));
+    if (gain_host) {
+      if (png_order) gain_rows.resize(pixels);
+      HIPCHK(c, hipMemcpyAsync(png_order ? gain_rows.data() : gain, gain_dev, pixels * sizeof(float), hipMemcpyDeviceToHost, stream));
+    }
+    return (int)RT_OK;
+  });
+  if (hipStreamSynchronize(stream_of(c)) != hipSuccess && !rc) return fail(c, RT_ERR_HIP, "denoise kernels");  // before mv is freed
+  if (rc) return rc;
+  if (gain_host && png_order) {
+    const size_t w = (size_t)m.grid.width, h = (size_t)m.grid.rows;
+    for (size_t j = 0; j < h; ++j) memcpy(gain + (h - 1 - j) * w, gain_rows.data() + j * w, w * sizeof(float));
+  }
+  return RT_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------- progressive accumulator
@@ -524,6 +569,7 @@ struct RT_INTERNAL rt_noise {
   Moments m;
   DevBuf<unsigned long long> totals;  // totals[0] = pixels above (image-wide), low word of totals[1] = max bits
   Timer timer;                        // around the last measure and its reduction
+  Timer denoise_timer;                // around the last denoise's kernels
 };
 
 namespace {
@@ -719,7 +765,7 @@ int noise_new(rt_accum* acc, rt_noise** out) {
   std::unique_ptr<rt_noise> nm(new rt_noise);
   nm->device = v.device;
   if (!nm->m.alloc(g) || !nm->totals.alloc(2)) return fail(c, RT_ERR_NOMEM, "hipMalloc noise monitor");
-  if (!nm->timer.create() || !nm->m.clear(v.stream)) return fail(c, RT_ERR_HIP, "set up noise monitor");
+  if (!nm->timer.create() || !nm->denoise_timer.create() || !nm->m.clear(v.stream)) return fail(c, RT_ERR_HIP, "set up noise monitor");
   nm->acc = acc;
   acc->noise = *out = nm.release();
   return RT_OK;
@@ -815,6 +861,14 @@ int rt_noise_map(rt_noise* nm, float* out) {
 
 float rt_noise_last_measure_ms(const rt_noise* nm) { return nm ? nm->timer.ms() : 0.0f; }
 
+int rt_denoise_monitor(rt_noise* nm, const rt_denoise_params* params, uint8_t* out, float* gain, int32_t png_order) {
+  if (!nm) return RT_ERR_ARG;
+  if (!nm->acc) return RT_ERR_STATE;  // detached
+  if (nm->fbs < 2) return fail(nm->acc->ctx, RT_ERR_STATE, "denoise needs at least 2 frame buffers");
+  return denoise_out(*nm->acc, nm->m, nullptr, nm->fbs, nm->denoise_timer, params, out, gain, png_order);
+}
+float rt_denoise_monitor_last_ms(const rt_noise* nm) { return nm ? nm->denoise_timer.ms() : 0.0f; }
+
 int rt_noise_save(rt_noise* nm, void* blob, size_t cap, size_t* need) {
   if (!nm) return RT_ERR_ARG;
   if (!nm->acc) return RT_ERR_STATE;  // detached
@@ -892,7 +946,8 @@ struct RT_INTERNAL rt_adapt : AccumCore {
                                       // once a reopen, which measures every tile, has made them active again)
   float measured = 0.0f;
   bool have_measure = false;
-  Timer retire_timer;  // around the last retire's measure kernel
+  Timer retire_timer;   // around the last retire's measure kernel
+  Timer denoise_timer;  // around the last denoise's kernels
 };
 
 namespace {
@@ -1063,7 +1118,7 @@ int rt_adapt_create(rt_ctx* c, const rt_render_args* a, int32_t chunk_fbs, rt_ad
   for (size_t t = 0; t < tiles; ++t) ad->active[t] = (int32_t)t;
   if (!ad->sums.alloc((size_t)ad->per_fb) || !ad->m.alloc(g) || !ad->ntile.alloc(tiles) || !ad->tile_n.alloc(tiles))
     return fail(c, RT_ERR_NOMEM, "hipMalloc adaptive accumulator");
-  if (!ad->add_timer.create() || !ad->retire_timer.create() || !ad->sums.clear(v.stream) || !ad->m.clear(v.stream) ||
+  if (!ad->add_timer.create() || !ad->retire_timer.create() || !ad->denoise_timer.create() || !ad->sums.clear(v.stream) || !ad->m.clear(v.stream) ||
       !ad->tile_n.clear(v.stream) || !ad->m.tile_max.clear(v.stream) || !ad->m.tile_above.clear(v.stream))
     return fail(c, RT_ERR_HIP, "set up adaptive accumulator");
   *out = ad.release();
@@ -1319,6 +1374,14 @@ int rt_adapt_image(rt_adapt* ad, uint8_t* out, int32_t png_order) {
     return (int)RT_OK;
   });
 }
+
+int rt_denoise_adaptive(rt_adapt* ad, const rt_denoise_params* params, uint8_t* out, float* gain, int32_t png_order) {
+  if (!ad) return RT_ERR_ARG;
+  for (int32_t n : ad->n_t)  // V divides by n_t - 1
+    if (n < 2) return fail(ad->ctx, RT_ERR_STATE, "denoise needs at least 2 frame buffers in every tile");
+  return denoise_out(*ad, ad->m, ad->tile_n.get(), 0, ad->denoise_timer, params, out, gain, png_order);
+}
+float rt_denoise_adaptive_last_ms(const rt_adapt* ad) { return ad ? ad->denoise_timer.ms() : 0.0f; }
 
 float rt_adapt_last_add_ms(const rt_adapt* ad) { return ad ? ad->add_timer.ms() : 0.0f; }
 float rt_adapt_last_retire_ms(const rt_adapt* ad) { return ad ? ad->retire_timer.ms() : 0.0f; }
