@@ -40,6 +40,10 @@
 //                           and print a JSON line with "denoised" and "denoise_ms"; needs two frame buffers.
 //                           With --progressive a noise monitor is attached for it (and saved and needed on
 //                           resuming, as with --until-noise) without stopping the draw
+//     --guided              with --denoise: the feature-guided filter (rt_guide_denoise_monitor / _adaptive with
+//                           the shipped gains) over the planes of an rt_guide of the scene
+//     --aov PREFIX          write PREFIX_normal.ppm and PREFIX_albedo.ppm: the noise-free normal and albedo
+//                           images of the camera's centre rays (rt_guide_render, rt_guide_image)
 //
 // Writes OUT.ppm (binary P6, top row first) and one JSON line per draw on stdout.  Files written
 // more than once go to a temporary name first and are renamed into place.
@@ -71,6 +75,8 @@ struct render_settings {
     rays_per_pixel = samples_per_pixel_per_fb * no_fb;
   }
 };
+
+rt_guide* g_guide = nullptr;  // --guided: the planes --denoise filters with
 
 int die(const char* what, const char* msg) {
   fprintf(stderr, "rt_main: %s: %s\n", what, msg ? msg : "");
@@ -193,7 +199,9 @@ int draw_progressive(rt_ctx* ctx, const char* name, const rt_render_args& a, int
     fflush(stdout);
   }
   if (denoised) {
-    if (rt_denoise_monitor(mon, nullptr, png.data(), nullptr, 1)) return die("rt_denoise_monitor", rt_last_error(ctx));
+    if (g_guide ? rt_guide_denoise_monitor(mon, g_guide, nullptr, nullptr, png.data(), nullptr, 1)
+                : rt_denoise_monitor(mon, nullptr, png.data(), nullptr, 1))
+      return die(g_guide ? "rt_guide_denoise_monitor" : "rt_denoise_monitor", rt_last_error(ctx));
     if (!write_file(denoised, head, png.data(), png.size())) return die("write", denoised);
     printf("{\"denoised\": \"%s\", \"fbs\": %d, \"denoise_ms\": %.3f}\n", denoised, i.args.fb_count, rt_denoise_monitor_last_ms(mon));
     fflush(stdout);
@@ -292,7 +300,9 @@ int draw_adaptive(rt_ctx* ctx, const char* name, const rt_render_args& a, int st
          pixel_fbs, measured ? rep.tiles_active : -1, noise_t, max_above);
   fflush(stdout);
   if (denoised) {
-    if (rt_denoise_adaptive(ad, nullptr, png.data(), nullptr, 1)) return die("rt_denoise_adaptive", rt_last_error(ctx));
+    if (g_guide ? rt_guide_denoise_adaptive(ad, g_guide, nullptr, nullptr, png.data(), nullptr, 1)
+                : rt_denoise_adaptive(ad, nullptr, png.data(), nullptr, 1))
+      return die(g_guide ? "rt_guide_denoise_adaptive" : "rt_denoise_adaptive", rt_last_error(ctx));
     if (!write_file(denoised, head, png.data(), png.size())) return die("write", denoised);
     printf("{\"denoised\": \"%s\", \"fbs\": %d, \"denoise_ms\": %.3f}\n", denoised, done, rt_denoise_adaptive_last_ms(ad));
     fflush(stdout);
@@ -308,7 +318,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: rt_main SCENE WIDTH SPP_PER_FB NO_FB OUT.ppm [--devices 0,1] [--gather rccl|host] "
                     "[--band-rows B] [--repeat K] [--depth D] [--height H] [--obj PATH] [--tex PATH] [--progressive K] [--checkpoint FILE] "
                     "[--until-noise T [--noisy-fraction F]] [--adaptive K --until-noise T [--max-above M] [--min-fbs F] "
-                    "[--adaptive-checkpoint FILE] [--dilate R] [--reopen]] [--denoise OUT2.ppm]\n");
+                    "[--adaptive-checkpoint FILE] [--dilate R] [--reopen]] [--denoise OUT2.ppm [--guided]] [--aov PREFIX]\n");
     return 2;
   }
   const char* name = argv[1];
@@ -319,7 +329,8 @@ int main(int argc, char** argv) {
   const char* out = argv[5];
   std::vector<int> devices;
   int gather = RT_GATHER_RCCL, band_rows = 4, repeat = 1;
-  const char *obj_path = nullptr, *tex_path = nullptr, *ckpt_path = nullptr, *adaptive_ckpt = nullptr, *denoised = nullptr;
+  const char *obj_path = nullptr, *tex_path = nullptr, *ckpt_path = nullptr, *adaptive_ckpt = nullptr, *denoised = nullptr, *aov = nullptr;
+  bool guided = false;
   int dilate = 0;
   bool reopen = false, have_resume_opts = false;
   int height = 0;
@@ -349,6 +360,8 @@ int main(int argc, char** argv) {
     else if (a == "--reopen") have_resume_opts = true, reopen = true;
     else if (a == "--until-noise") until_noise = true, noise_t = (float)atof(v), ++k;
     else if (a == "--denoise") denoised = v, ++k;
+    else if (a == "--guided") guided = true;
+    else if (a == "--aov") aov = v, ++k;
     else if (a == "--noisy-fraction") have_fraction = true, noisy_fraction = atof(v), ++k;
     else return die("unknown option", argv[k]);
   }
@@ -368,6 +381,8 @@ int main(int argc, char** argv) {
   if (!have_adaptive && (until_noise || have_fraction) && progressive <= 0) return die("--until-noise / --noisy-fraction", "need --progressive K");
   if (have_fraction && !until_noise) return die("--noisy-fraction", "needs --until-noise T");
   if (denoised && !have_adaptive && progressive <= 0) return die("--denoise", "needs --progressive K or --adaptive K");
+  if (guided && !denoised) return die("--guided", "needs --denoise OUT2.ppm");
+  if ((guided || aov) && !devices.empty()) return die("--guided / --aov", "one GPU only (no --devices)");
   if (denoised && s.no_fb > 32768) return die("--denoise", "a noise monitor accepts at most 32768 frame buffers");
   if (until_noise && s.no_fb > 32768) return die("--until-noise", "a noise monitor accepts at most 32768 frame buffers");
 
@@ -428,9 +443,24 @@ int main(int argc, char** argv) {
     if (rc) return die("rt_multi_create", gather == RT_GATHER_RCCL ? "RCCL communicator (distinct devices?)" : "");
     if (rt_multi_upload(multi, soa)) return die("rt_multi_upload", rt_multi_last_error(multi));
   }
+  rt_guide* guide = nullptr;
+  if (guided || aov) {  // the feature planes of the camera's centre rays, from the guide's own copy of the scene
+    if (rt_guide_create(soa, 0, &guide)) return die("rt_guide_create", name);
+    if (rt_guide_render(guide, a.width, a.height)) return die("rt_guide_render", name);
+    if (guided) g_guide = guide;
+    char head[64];
+    snprintf(head, sizeof(head), "P6\n%d %d\n255\n", a.width, a.height);
+    for (int which = 0; aov && which < 2; ++which) {
+      const std::string path = std::string(aov) + (which == RT_GUIDE_NORMAL ? "_normal.ppm" : "_albedo.ppm");
+      if (rt_guide_image(guide, which, png.data(), 1)) return die("rt_guide_image", path.c_str());
+      if (!write_file(path, head, png.data(), png.size())) return die("write", path.c_str());
+    }
+    if (aov) printf("{\"aov\": \"%s\", \"guide_ms\": %.3f}\n", aov, rt_guide_last_ms(guide));
+  }
   if (have_adaptive) {
     if (!ctx) return die("--adaptive", "one GPU only (no --devices)");
     const int rc = draw_adaptive(ctx, name, a, adaptive, out, png, noise_t, max_above, min_fbs, adaptive_ckpt, dilate, reopen, denoised);
+    if (guide) rt_guide_destroy(guide);
     rt_ctx_destroy(ctx);
     rt_scene_free(scene);
     return rc;
@@ -440,6 +470,7 @@ int main(int argc, char** argv) {
     if (progressive < 0 || a.fb_count < 1) return die("--progressive", "K and NO_FB must be at least 1");
     const int rc = draw_progressive(ctx, name, a, progressive > 0 ? progressive : a.fb_count, ckpt_path, out, png,
                                       until_noise, noise_t, noisy_fraction, denoised);
+    if (guide) rt_guide_destroy(guide);
     rt_ctx_destroy(ctx);
     rt_scene_free(scene);
     return rc;
@@ -472,6 +503,7 @@ int main(int argc, char** argv) {
   fprintf(f, "P6\n%d %d\n255\n", a.width, a.height);
   fwrite(png.data(), 1, png.size(), f);
   fclose(f);
+  if (guide) rt_guide_destroy(guide);
   if (ctx) rt_ctx_destroy(ctx);
   if (multi) rt_multi_destroy(multi);
   rt_scene_free(scene);

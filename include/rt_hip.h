@@ -695,6 +695,102 @@ float rt_denoise_adaptive_last_ms(const rt_adapt* ad);
 int rt_denoise_monitor_blob(const void* blob, size_t n, const rt_denoise_params* params, uint8_t* out, float* gain);
 int rt_denoise_adaptive_blob(const void* blob, size_t n, const rt_denoise_params* params, uint8_t* out, float* gain);
 
+/* ------------------------------------------------------------------ ray casts and feature buffers */
+/* A guide answers world->hit(r, 0.001, inf) for rays of the caller's: the hit point, the normal the shading
+ * sees (set_face_normal applied), the material, the material's texture value there and the primitive.  No random
+ * number is drawn, nothing of a context is touched, and the render kernels are not involved: a guide holds its
+ * own validated copy of the scene.  It serves picking, depth and normal images, looking into a scene, and the
+ * feature buffers of the guided denoise below.  (The names begin with rt_guide_ because the denoiser's family is
+ * closed.)
+ *
+ * The answer is the reference's, operation for operation (csrc/rt_first_hit.h, compiled by the device kernels
+ * and by the host-only calls alike, which therefore agree bit for bit): the top-level list in order, lists,
+ * transforms, boxes, the BVH visit of RT_FLAG_EXACT_TRAVERSAL.  albedo is the material's texture at (u, v, p):
+ * a diffuse_light's emit texture, (1, 1, 1) for a dielectric.  An RT_OBJ_MEDIUM is seen as its boundary: the
+ * boundary's nearest hit with t > 0.001, with the phase material as `material` and that material's texture as
+ * albedo.  A BVH of more than 30 inner levels is RT_ERR_SCENE. */
+typedef struct rt_guide_hit {
+  float t;            /* 0 for a miss */
+  float p[3];
+  float n[3];         /* as the shading sees it: against the ray; not normalised for a flat triangle; 0 for a miss */
+  float albedo[3];    /* the scene's background for a miss */
+  float u, v;
+  int32_t prim;       /* index into rt_scene_soa.prims (a box is one primitive); -1 for a miss */
+  int32_t material;   /* -1 for a miss */
+  int32_t front;      /* hit_record::front_face */
+  int32_t pad;
+} rt_guide_hit;       /* 64 bytes */
+typedef struct rt_guide rt_guide;
+enum rt_guide_plane { RT_GUIDE_NORMAL = 0, RT_GUIDE_ALBEDO = 1 };
+
+/* rt_scene_validate, then a copy of the scene in the memory of hip_device, with rtacc's scene fingerprint (the
+ * one rt_accum_info carries). */
+int rt_guide_create(const rt_scene_soa* scene, int hip_device, rt_guide** out);
+int rt_guide_destroy(rt_guide* g);
+/* n rays of 8 floats each -- o[3], d[3], time, unused: the layout the oracle captures -- into n hits.  rays and
+ * out are each a device or a host pointer (host buffers are staged through temporary device memory).  n = 0 is
+ * RT_OK. */
+int rt_guide_cast(rt_guide* g, const float* rays, long long n, rt_guide_hit* out);
+/* The centre ray of every pixel of a width x height image into the guide's planes (28 bytes per pixel, kept
+ * until the next rt_guide_render or the destroy): camera.h get_ray at s = (i + 0.5f) / width,
+ * t = (j + 0.5f) / height, j = 0 the bottom row, with a lens offset of 0 and time = time0 + 0.5f (time1 - time0). */
+int rt_guide_render(rt_guide* g, int32_t width, int32_t height);
+/* The planes of the last rt_guide_render (RT_ERR_STATE before one): normal and albedo [height][width][3]
+ * floats, depth [height][width] floats (t; 0 for a miss), prim [height][width].  Any pointer may be NULL; each
+ * is a device or a host pointer.  png_order = 0: row 0 is the bottom row, as a frame buffer; 1: top row first,
+ * host pointers only. */
+int rt_guide_planes(rt_guide* g, float* normal, float* albedo, float* depth, int32_t* prim, int32_t png_order);
+/* An 8-bit picture of a plane, [height][width][3], out a device or a host pointer: RT_GUIDE_NORMAL is
+ * quant((n + 1.0f) / 2.0f) per component (a flat triangle's unnormalised normal saturates), RT_GUIDE_ALBEDO is
+ * quant(albedo), with write_frame_buffer's quantisation. */
+int rt_guide_image(rt_guide* g, int32_t which, uint8_t* out, int32_t png_order);
+/* Device time in ms of the last cast or render kernel; 0 before one. */
+float rt_guide_last_ms(const rt_guide* g);
+/* Host only (no GPU; csrc/rt_guide_host.cpp): the same answers from the same code.  Host pointers; the planes
+ * may each be NULL, row 0 the bottom row. */
+int rt_guide_cast_host(const rt_scene_soa* scene, const float* rays, long long n, rt_guide_hit* out);
+int rt_guide_render_host(const rt_scene_soa* scene, int32_t width, int32_t height, float* normal, float* albedo, float* depth,
+                         int32_t* prim);
+
+/* The guided denoise: the denoiser above with the feature planes of a guide as a second opinion on every
+ * weight (Rousselle, Manzi, Zwicker 2013: the minimum of the colour weight and the feature weight).  For pixel
+ * p, a search offset o other than the centre and q = p + o, on the centre pixels alone (no patch sum), with N
+ * the normal plane, A the albedo plane and z the depth plane; a pixel is a miss when its z equals 0.  In float,
+ * one rounded operation per operator, left to right:
+ *
+ *   fn = sum over c of (N_p,c - N_q,c)^2          ((d0 d0 + d1 d1) + d2 d2)
+ *   fa = sum over c of (A_p,c - A_q,c)^2
+ *   r  = (z_p - z_q) / (z_p + z_q);  fz = r r
+ *   xf = fn normal_gain + fa albedo_gain + fz depth_gain
+ *   exactly one of p, q a miss: xf = 64;  both: xf = 0;  a NaN xf counts as 64
+ *
+ * and the weight's x becomes fmaxf(x, xf) after its clamp at 0, before s = 1 - x / 8.  Everything else is the
+ * denoiser's definition: P, Num and Den stay integer sums, the centre offset keeps W = 65536 whatever the
+ * planes hold.  With every gain 0 and no pixel a miss (or every pixel) the result is rt_denoise_monitor's, byte
+ * for byte.  Gains are >= 0 (anything else, a NaN included, is RT_ERR_ARG). */
+typedef struct rt_guide_params {
+  float normal_gain, albedo_gain, depth_gain;
+  int32_t pad;
+} rt_guide_params;
+void rt_guide_params_default(rt_guide_params* p);
+/* rt_denoise_monitor / rt_denoise_adaptive with the planes of g.  RT_ERR_STATE unless g has rendered planes of
+ * the accumulator's width x height, its scene fingerprint is the accumulator's, and it lives on the
+ * accumulator's device; otherwise every check, output and error of the unguided call (on an error out and gain
+ * are untouched).  params or gparams = NULL takes the defaults.  The guide is read only. */
+int rt_guide_denoise_monitor(rt_noise* nm, rt_guide* g, const rt_denoise_params* params, const rt_guide_params* gparams,
+                             uint8_t* out, float* gain, int32_t png_order);
+int rt_guide_denoise_adaptive(rt_adapt* ad, rt_guide* g, const rt_denoise_params* params, const rt_guide_params* gparams,
+                              uint8_t* out, float* gain, int32_t png_order);
+/* Host only: rt_denoise_monitor_blob / rt_denoise_adaptive_blob with host planes (rt_guide_planes' layout with
+ * png_order = 0) of plane_height x plane_width pixels; RT_ERR_ARG when that is not the blob's image size, for a
+ * null plane or a bad gain, besides the unguided calls' errors. */
+int rt_guide_denoise_monitor_blob(const void* blob, size_t n, const rt_denoise_params* params, const rt_guide_params* gparams,
+                                  const float* normal, const float* albedo, const float* depth, int32_t plane_width,
+                                  int32_t plane_height, uint8_t* out, float* gain);
+int rt_guide_denoise_adaptive_blob(const void* blob, size_t n, const rt_denoise_params* params, const rt_guide_params* gparams,
+                                   const float* normal, const float* albedo, const float* depth, int32_t plane_width,
+                                   int32_t plane_height, uint8_t* out, float* gain);
+
 /* ------------------------------------------------------------------ host scene library */
 /* Builds one of the reference scenes (scenes.h) on the host: "basic", "first", "big1" (alias
  * "random"), "two_spheres", "two_perlin", "cornell", "cornell_smoke", "triangle", "triangles",

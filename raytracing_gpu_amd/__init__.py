@@ -183,6 +183,24 @@ class rt_denoise_params(ctypes.Structure):
 
 NOISE_MAX_FBS = 32768  # frame buffers a noise monitor accepts (include/rt_hip.h)
 
+class rt_guide_hit(ctypes.Structure):
+    """include/rt_hip.h rt_guide_hit (64 bytes)."""
+    _fields_ = [("t", c_float), ("p", c_float * 3), ("n", c_float * 3), ("albedo", c_float * 3), ("u", c_float), ("v", c_float),
+                ("prim", c_int32), ("material", c_int32), ("front", c_int32), ("pad", c_int32)]
+
+
+GUIDE_HIT_DTYPE = np.dtype([("t", "<f4"), ("p", "<f4", 3), ("n", "<f4", 3), ("albedo", "<f4", 3), ("u", "<f4"), ("v", "<f4"),
+                            ("prim", "<i4"), ("material", "<i4"), ("front", "<i4"), ("pad", "<i4")])
+
+
+class rt_guide_params(ctypes.Structure):
+    """include/rt_hip.h rt_guide_params."""
+    _fields_ = [("normal_gain", c_float), ("albedo_gain", c_float), ("depth_gain", c_float), ("pad", c_int32)]
+
+    def as_dict(self) -> dict:
+        return {"normal_gain": float(self.normal_gain), "albedo_gain": float(self.albedo_gain), "depth_gain": float(self.depth_gain)}
+
+
 # Every entry point of include/rt_hip.h: name -> (restype, argtypes)
 ABI = {
     "rt_ctx_create": (c_int, [c_int, POINTER(c_void_p)]),
@@ -257,6 +275,24 @@ ABI = {
     "rt_denoise_adaptive_last_ms": (c_float, [c_void_p]),
     "rt_denoise_monitor_blob": (c_int, [c_void_p, c_size_t, POINTER(rt_denoise_params), c_void_p, c_void_p]),
     "rt_denoise_adaptive_blob": (c_int, [c_void_p, c_size_t, POINTER(rt_denoise_params), c_void_p, c_void_p]),
+    "rt_guide_create": (c_int, [POINTER(rt_scene_soa), c_int, POINTER(c_void_p)]),
+    "rt_guide_destroy": (c_int, [c_void_p]),
+    "rt_guide_cast": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p]),
+    "rt_guide_render": (c_int, [c_void_p, c_int32, c_int32]),
+    "rt_guide_planes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32]),
+    "rt_guide_image": (c_int, [c_void_p, c_int32, c_void_p, c_int32]),
+    "rt_guide_last_ms": (c_float, [c_void_p]),
+    "rt_guide_cast_host": (c_int, [POINTER(rt_scene_soa), c_void_p, ctypes.c_longlong, c_void_p]),
+    "rt_guide_render_host": (c_int, [POINTER(rt_scene_soa), c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rt_guide_params_default": (None, [POINTER(rt_guide_params)]),
+    "rt_guide_denoise_monitor": (c_int, [c_void_p, c_void_p, POINTER(rt_denoise_params), POINTER(rt_guide_params), c_void_p,
+                                         c_void_p, c_int32]),
+    "rt_guide_denoise_adaptive": (c_int, [c_void_p, c_void_p, POINTER(rt_denoise_params), POINTER(rt_guide_params), c_void_p,
+                                          c_void_p, c_int32]),
+    "rt_guide_denoise_monitor_blob": (c_int, [c_void_p, c_size_t, POINTER(rt_denoise_params), POINTER(rt_guide_params), c_void_p,
+                                              c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "rt_guide_denoise_adaptive_blob": (c_int, [c_void_p, c_size_t, POINTER(rt_denoise_params), POINTER(rt_guide_params), c_void_p,
+                                               c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "rt_scene_build": (c_int, [c_char_p, POINTER(c_void_p)]),
     "rt_scene_build_ex": (c_int, [c_char_p, c_void_p, POINTER(c_void_p)]),
     "rt_obj_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
@@ -322,6 +358,29 @@ def _denoise_call(check, fn, what, handle, params, rows, width, png_order, gain)
     g = np.zeros((rows, width), np.float32) if gain else None
     check(fn(handle, ctypes.byref(p), img.ctypes.data, g.ctypes.data if gain else None, 1 if png_order else 0), what)
     return (img, g) if gain else img
+
+
+def guide_params(params=None, **kw) -> rt_guide_params:
+    """The gains of the guided denoise (include/rt_hip.h): the shipped defaults, or a copy of params (an
+    rt_guide_params, a dict of its fields, True or None for the defaults), with the fields of kw set."""
+    p = rt_guide_params()
+    if isinstance(params, rt_guide_params):
+        ctypes.memmove(ctypes.byref(p), ctypes.byref(params), ctypes.sizeof(p))
+    else:
+        lib().rt_guide_params_default(ctypes.byref(p))
+        if isinstance(params, dict):
+            kw = {**params, **kw}
+    for k, v in kw.items():
+        if k not in ("normal_gain", "albedo_gain", "depth_gain"):
+            raise TypeError(f"rt_guide_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _guided(fn, guide, guide_params_):
+    """fn(handle, guide, params, gains, image, gain, png_order) in the shape _denoise_call calls."""
+    gp = guide_params(guide_params_)
+    return lambda h, p, img, g, order: fn(h, guide._h, p, ctypes.byref(gp), img, g, order)
 
 
 class RtError(RuntimeError):
@@ -751,11 +810,16 @@ class NoiseMonitor:
         """Device time of the last measure() / map() kernel."""
         return float(lib().rt_noise_last_measure_ms(self._h))
 
-    def denoise(self, params=None, png_order: bool = True, gain: bool = False):
+    def denoise(self, params=None, png_order: bool = True, gain: bool = False, guide=None, guide_params=None):
         """The denoised image of the frame buffers so far (rt_denoise_monitor: a variance-guided NL-means
         filter on the monitor's moments; needs two frame buffers and the whole-image tiling): (rows, width, 3)
         uint8, top row first with png_order, and with gain=True also the (rows, width) float32 number of
-        pixels' worth every pixel was averaged over.  params: see denoise_params().  Changes no state."""
+        pixels' worth every pixel was averaged over.  params: see denoise_params().  Changes no state.
+        guide: a Guide of the same scene that has rendered planes of the image's size (rt_guide_denoise_monitor:
+        the feature-guided weights), with guide_params as guide_params() takes them."""
+        if guide is not None:
+            return _denoise_call(self._check, _guided(lib().rt_guide_denoise_monitor, guide, guide_params),
+                                 "rt_guide_denoise_monitor", self._h, params, self._rows, self._width, png_order, gain)
         return _denoise_call(self._check, lib().rt_denoise_monitor, "rt_denoise_monitor", self._h, params, self._rows,
                              self._width, png_order, gain)
 
@@ -911,9 +975,13 @@ class AdaptiveAccumulator:
         """Device time of the last retire()'s measure kernel."""
         return float(lib().rt_adapt_last_retire_ms(self._h))
 
-    def denoise(self, params=None, png_order: bool = True, gain: bool = False):
+    def denoise(self, params=None, png_order: bool = True, gain: bool = False, guide=None, guide_params=None):
         """NoiseMonitor.denoise() with every pixel at its own tile's count (rt_denoise_adaptive; every tile
-        needs two frame buffers): tiles that retired early at a higher noise are smoothed more."""
+        needs two frame buffers): tiles that retired early at a higher noise are smoothed more.  guide,
+        guide_params: as NoiseMonitor.denoise() (rt_guide_denoise_adaptive)."""
+        if guide is not None:
+            return _denoise_call(self.ctx._check, _guided(lib().rt_guide_denoise_adaptive, guide, guide_params),
+                                 "rt_guide_denoise_adaptive", self._h, params, self._rows, self._width, png_order, gain)
         return _denoise_call(self.ctx._check, lib().rt_denoise_adaptive, "rt_denoise_adaptive", self._h, params, self._rows,
                              self._width, png_order, gain)
 
@@ -956,9 +1024,16 @@ def read_noise(path: str, threshold: float) -> tuple[dict, np.ndarray, np.ndarra
     return {**d, **rep.as_dict()}, tile_max, tile_above, nmap
 
 
-def _denoise_file(path: str, info_fn, fn, what: str, params, gain: bool):
+def _denoise_file(path: str, info_fn, fn, what: str, params, gain: bool, guide=None, guide_params_=None):
     with open(path, "rb") as f:
         blob = f.read()
+    if guide is not None:  # planes as Guide.planes(png_order=False) / guide_host() give them
+        nrm, alb, dep = (np.ascontiguousarray(guide[k], np.float32) for k in ("normal", "albedo", "depth"))
+        if nrm.shape != dep.shape + (3,) or alb.shape != nrm.shape or dep.ndim != 2:
+            raise ValueError("guide planes: normal and albedo (rows, width, 3), depth (rows, width)")
+        gp, plain = guide_params(guide_params_), fn
+        fn = lambda b, n, p, img, g: plain(b, n, p, ctypes.byref(gp), nrm.ctypes.data, alb.ctypes.data, dep.ctypes.data,  # noqa: E731
+                                           dep.shape[1], dep.shape[0], img, g)
     i = rt_accum_info()
     rc = info_fn(blob, len(blob), ctypes.byref(i))
     if rc != 0:
@@ -972,17 +1047,129 @@ def _denoise_file(path: str, info_fn, fn, what: str, params, gain: bool):
                          i.n_values // (3 * i.args.width), i.args.width, False, gain)
 
 
-def denoise_checkpoint(path: str, params=None, gain: bool = False):
+def denoise_checkpoint(path: str, params=None, gain: bool = False, guide=None, guide_params=None):
     """NoiseMonitor.denoise() of a monitor's side file (the checkpoint's ".noise"), by the host-only
     rt_denoise_monitor_blob (no context, no GPU), byte-identical to the device's: (rows, width, 3) uint8 with
-    rows ascending (bottom row first), and with gain=True the (rows, width) float32 gain too."""
+    rows ascending (bottom row first), and with gain=True the (rows, width) float32 gain too.  guide: a dict of
+    the planes "normal", "albedo", "depth" with rows ascending (guide_host(), Guide.planes(png_order=False)):
+    the guided denoise, by rt_guide_denoise_monitor_blob."""
+    if guide is not None:
+        return _denoise_file(path, lib().rt_noise_blob_info, lib().rt_guide_denoise_monitor_blob, "rt_guide_denoise_monitor_blob",
+                             params, gain, guide, guide_params)
     return _denoise_file(path, lib().rt_noise_blob_info, lib().rt_denoise_monitor_blob, "rt_denoise_monitor_blob", params, gain)
 
 
-def denoise_adaptive_checkpoint(path: str, params=None, gain: bool = False):
-    """AdaptiveAccumulator.denoise() of an adaptive checkpoint file, by the host-only rt_denoise_adaptive_blob."""
+def denoise_adaptive_checkpoint(path: str, params=None, gain: bool = False, guide=None, guide_params=None):
+    """AdaptiveAccumulator.denoise() of an adaptive checkpoint file, by the host-only rt_denoise_adaptive_blob
+    (with guide planes: rt_guide_denoise_adaptive_blob, see denoise_checkpoint)."""
+    if guide is not None:
+        return _denoise_file(path, lib().rt_adaptive_blob_info, lib().rt_guide_denoise_adaptive_blob,
+                             "rt_guide_denoise_adaptive_blob", params, gain, guide, guide_params)
     return _denoise_file(path, lib().rt_adaptive_blob_info, lib().rt_denoise_adaptive_blob, "rt_denoise_adaptive_blob", params,
                          gain)
+
+
+# ---------------------------------------------------------------- ray casts and feature buffers
+def _soa_of(scene) -> rt_scene_soa:
+    return getattr(scene, "soa", scene)  # a Scene (or anything that carries its rt_scene_soa), or the struct itself
+
+
+def _rays(rays) -> np.ndarray:
+    r = np.ascontiguousarray(rays, np.float32)
+    if r.ndim != 2 or r.shape[1] != 8:
+        raise ValueError("rays: (n, 8) float32 -- o[3], d[3], time, unused")
+    return r
+
+
+class Guide:
+    """rt_guide of include/rt_hip.h: ray casts into a scene (a Scene or an rt_scene_soa) and the noise-free
+    feature planes of its camera -- normal, albedo, depth, primitive id -- for picking, AOV images and the
+    guided denoise (NoiseMonitor.denoise(guide=...)).  It holds its own copy of the scene on the device."""
+
+    def __init__(self, scene, device: int = 0):
+        h = c_void_p()
+        rc = lib().rt_guide_create(ctypes.byref(_soa_of(scene)), device, ctypes.byref(h))
+        if rc != 0:
+            raise RtError(f"rt_guide_create failed ({rc})", rc)
+        self._h = h
+        self.width = self.height = 0
+
+    def _check(self, rc: int, what: str) -> None:
+        if rc != 0:
+            raise RtError(f"{what} failed ({rc})", rc)
+
+    def cast(self, rays) -> np.ndarray:
+        """The first hit of every ray ((n, 8) float32: o, d, time, unused) as a structured array of
+        GUIDE_HIT_DTYPE: t, p, n, albedo, u, v, prim (-1: a miss), material, front."""
+        r = _rays(rays)
+        out = np.zeros(len(r), GUIDE_HIT_DTYPE)
+        self._check(lib().rt_guide_cast(self._h, r.ctypes.data, len(r), out.ctypes.data), "rt_guide_cast")
+        return out
+
+    def cast_into(self, rays_ptr: int, n: int, out_ptr: int) -> None:
+        """cast() between caller memory (device or host addresses)."""
+        self._check(lib().rt_guide_cast(self._h, c_void_p(rays_ptr), n, c_void_p(out_ptr)), "rt_guide_cast")
+
+    def render(self, width: int, height: int) -> "Guide":
+        """The centre ray of every pixel into the guide's planes."""
+        self._check(lib().rt_guide_render(self._h, width, height), "rt_guide_render")
+        self.width, self.height = width, height
+        return self
+
+    def planes(self, png_order: bool = False) -> dict:
+        """{"normal", "albedo": (H, W, 3) float32, "depth": (H, W) float32, "prim": (H, W) int32} of the last
+        render(); row 0 the bottom row unless png_order."""
+        H, W = self.height, self.width
+        d = {"normal": np.zeros((H, W, 3), np.float32), "albedo": np.zeros((H, W, 3), np.float32),
+             "depth": np.zeros((H, W), np.float32), "prim": np.zeros((H, W), np.int32)}
+        self._check(lib().rt_guide_planes(self._h, d["normal"].ctypes.data, d["albedo"].ctypes.data, d["depth"].ctypes.data,
+                                          d["prim"].ctypes.data, 1 if png_order else 0), "rt_guide_planes")
+        return d
+
+    def image(self, which: str, png_order: bool = True) -> np.ndarray:
+        """The 8-bit picture of the "normal" or "albedo" plane, (H, W, 3) uint8."""
+        if which not in ("normal", "albedo"):
+            raise ValueError('which: "normal" or "albedo"')
+        out = np.zeros((self.height, self.width, 3), np.uint8)
+        self._check(lib().rt_guide_image(self._h, 0 if which == "normal" else 1, out.ctypes.data, 1 if png_order else 0),
+                    "rt_guide_image")
+        return out
+
+    def last_ms(self) -> float:
+        """Device time of the last cast() / render() kernel."""
+        return float(lib().rt_guide_last_ms(self._h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().rt_guide_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cast_host(scene, rays) -> np.ndarray:
+    """Guide.cast() on the host (rt_guide_cast_host: no GPU), bit-identical to the device's."""
+    r = _rays(rays)
+    out = np.zeros(len(r), GUIDE_HIT_DTYPE)
+    rc = lib().rt_guide_cast_host(ctypes.byref(_soa_of(scene)), r.ctypes.data, len(r), out.ctypes.data)
+    if rc != 0:
+        raise RtError(f"rt_guide_cast_host failed ({rc})", rc)
+    return out
+
+
+def guide_host(scene, width: int, height: int) -> dict:
+    """Guide.render(width, height).planes() on the host (rt_guide_render_host: no GPU)."""
+    d = {"normal": np.zeros((height, width, 3), np.float32), "albedo": np.zeros((height, width, 3), np.float32),
+         "depth": np.zeros((height, width), np.float32), "prim": np.zeros((height, width), np.int32)}
+    rc = lib().rt_guide_render_host(ctypes.byref(_soa_of(scene)), width, height, d["normal"].ctypes.data, d["albedo"].ctypes.data,
+                                    d["depth"].ctypes.data, d["prim"].ctypes.data)
+    if rc != 0:
+        raise RtError(f"rt_guide_render_host failed ({rc})", rc)
+    return d
 
 
 def read_checkpoint(path: str) -> tuple[dict, np.ndarray]:
@@ -1037,6 +1224,23 @@ def read_adaptive_checkpoint(path: str, threshold: float | None = None) -> tuple
     return d, img, counts, active.astype(bool), rep.as_dict(), nmap
 
 
+def _final_denoise(target, denoise, curr_scene: Scene, settings: render_settings, device: int):
+    """target.denoise(denoise).  A dict with guide=True (and, if wanted, guide_params=...) beside the denoiser's
+    fields takes the guided filter: a Guide of the scene on the draw's device, rendered at the image's size."""
+    if isinstance(denoise, dict) and ("guide" in denoise or "guide_params" in denoise):
+        fields = dict(denoise)
+        use, gains = fields.pop("guide", False), fields.pop("guide_params", None)
+        if use:
+            g = Guide(curr_scene, device)
+            try:
+                g.render(settings.image_width, settings.image_height)
+                return target.denoise(fields, guide=g, guide_params=gains)
+            finally:
+                g.close()
+        denoise = fields
+    return target.denoise(denoise)
+
+
 def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context | None = None, every: int = 1,
                      on_image=None, checkpoint: str | None = None, chunk_fbs: int | None = None,
                      cam_mode: int = RT_CAM_REF_SLOT0, seed: int = 1984, until_noise: float | None = None,
@@ -1059,7 +1263,8 @@ def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context 
     file: a missing one, or one whose header differs from the checkpoint's, raises RtError -- the
     statistics are never silently restarted from a later frame buffer.
 
-    denoise=True (the shipped parameters) or parameters as denoise_params() takes them: a noise monitor is
+    denoise=True (the shipped parameters) or parameters as denoise_params() takes them (a dict may also hold
+    guide=True for the feature-guided filter, and guide_params): a noise monitor is
     attached if until_noise has not attached one (it never stops the draw then), and the image returned is
     NoiseMonitor.denoise() of the final state instead of the plain one (needs two frame buffers); on_image
     still gets the plain images.  None leaves the function exactly as it is without it."""
@@ -1119,7 +1324,7 @@ def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context 
             if on_image is not None:
                 on_image(img, acc.done)
         if denoise is not None:
-            img = mon.denoise(denoise)
+            img = _final_denoise(mon, denoise, curr_scene, settings, ctx.device)
         return img, total
     finally:
         if acc is not None:
@@ -1150,7 +1355,8 @@ def draw_adaptive(curr_scene: Scene, settings: render_settings, ctx: Context | N
     their neighbours within dilate) active again, each from its own count: a finished draw refined to a
     tighter threshold.
 
-    denoise=True (the shipped parameters) or parameters as denoise_params() takes them: the image returned is
+    denoise=True (the shipped parameters) or parameters as denoise_params() takes them (a dict may also hold
+    guide=True for the feature-guided filter, and guide_params): the image returned is
     AdaptiveAccumulator.denoise() of the final state, every pixel at its own tile's count, instead of the plain
     one (every tile needs two frame buffers); on_image still gets the plain images."""
     if settings.image_height <= 0:
@@ -1200,7 +1406,7 @@ def draw_adaptive(curr_scene: Scene, settings: render_settings, ctx: Context | N
             if on_image is not None:
                 on_image(ad.image(png_order=True), done)
         if done:
-            img = ad.image(png_order=True) if denoise is None else ad.denoise(denoise)
+            img = ad.image(png_order=True) if denoise is None else _final_denoise(ad, denoise, curr_scene, settings, ctx.device)
         return img, total, ad.counts()
     finally:
         if ad is not None:

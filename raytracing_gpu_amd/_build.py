@@ -17,8 +17,8 @@ MULTI_LIB = os.path.join(PKG, "librt_multi.so")
 EXAMPLES = os.path.join(ROOT, "examples")
 RT_MAIN = os.path.join(EXAMPLES, "bin", "rt_main")
 
-HIP_SOURCES = ["rt_kernels.hip", "rt_progressive.hip", "rt_denoise.hip", "rt_scene.cpp", "rt_obj.cpp", "rt_image.cpp", "rt_accum_blob.cpp",
-               "rt_noise_blob.cpp", "rt_adapt_blob.cpp", "rt_denoise_blob.cpp", "rt_validate.cpp"]
+HIP_SOURCES = ["rt_kernels.hip", "rt_progressive.hip", "rt_denoise.hip", "rt_guide.hip", "rt_scene.cpp", "rt_obj.cpp", "rt_image.cpp",
+               "rt_accum_blob.cpp", "rt_noise_blob.cpp", "rt_adapt_blob.cpp", "rt_denoise_blob.cpp", "rt_guide_host.cpp", "rt_validate.cpp"]
 # every header of csrc/ (rt_diag.h included): an edit to any of them rebuilds the library and changes
 # kernel_build_id() (tests/test_build_cpu.py checks that each local #include is covered)
 HIP_DEPS = HIP_SOURCES + sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/rt_hip.h"
+#include "rt_denoise_math.h"
 
 #pragma GCC visibility push(hidden)
 namespace rtdn {
@@ -13,9 +14,12 @@ namespace rtdn {
 // The prepare pass and the filter, queued on stream: the moments s1, s2 of rows x width pixels (whole image,
 // rows ascending) after n >= 2 frame buffers -- or, with tile_n, after tile_n[noise tile] >= 2 each -- filtered
 // with p (checked by the caller) into out [rows][width][3] and gain [rows][width] (may be null), both device
-// memory.  mv: scratch of rows x width x 3 float2.
+// memory.  mv: scratch of rows x width x 3 float2.  guide (may be null): the feature planes of rows x width
+// pixels in device memory and the gains (checked by the caller) of the guided denoise, which runs the filter's
+// GUIDED instances; without it the launches are the unguided ones.
 hipError_t launch(hipStream_t stream, const uint32_t* s1, const unsigned long long* s2, const int32_t* tile_n, int n, int rows,
-                  int width, const rt_denoise_params& p, float2* mv, uint8_t* out, float* gain);
+                  int width, const rt_denoise_params& p, float2* mv, uint8_t* out, float* gain,
+                  const GuideView* guide = nullptr);
 
 }  // namespace rtdn
 #pragma GCC visibility pop

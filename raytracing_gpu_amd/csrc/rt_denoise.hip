@@ -48,10 +48,13 @@ __global__ __launch_bounds__(kBlock) void denoise_prepare_kernel(const uint32_t*
 // H, the weight, and Num += W Q_q, Den += W in registers.  The next offset's D is written after the barrier
 // that follows the last read of D, and its H after the barrier that follows the last read of H: two barriers
 // per offset.  Zeros in D stand for the patch offsets the definition leaves out, and cnt counts the others.
-template <int F, int TW, int TH>
+// GUIDED (the guided denoise): the lane's own seven feature values stay in registers over all offsets and the
+// partner's are read from global memory per offset (the planes are not staged: LDS is full at the largest
+// radii); the weight takes the feature term.  The unguided instances compile none of it.
+template <int F, int TW, int TH, bool GUIDED>
 __global__ __launch_bounds__(TW * TH) void denoise_filter_kernel(const float2* __restrict__ mv, int rows, int width, int R,
                                                              float alpha, float kk, float eps, uint8_t* __restrict__ out,
-                                                             float* __restrict__ gain) {
+                                                             float* __restrict__ gain, const rtdn::GuideView guide) {
   constexpr int SW = TW + 2 * F, SH = TH + 2 * F, NT = TW * TH;
   constexpr int kSlotsD = (SW * SH + NT - 1) / NT, kSlotsH = (SH * TW + NT - 1) / NT;
   extern __shared__ float lds[];
@@ -96,6 +99,13 @@ __global__ __launch_bounds__(TW * TH) void denoise_filter_kernel(const float2* _
   const bool p_in = py < rows && px < width;
   const int p_at = (ly + R + F) * HS + lx + R + F;
   unsigned long long num[3] = {0, 0, 0}, den = 0;
+  rtdn::Feature fp = {};
+  if (GUIDED && p_in) {
+    const long long p = (long long)py * width + px;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) fp.n[j] = guide.normal[3 * p + j], fp.a[j] = guide.albedo[3 * p + j];
+    fp.z = guide.depth[p];
+  }
 
   for (int oy = -R; oy <= R; ++oy)
     for (int ox = -R; ox <= R; ++ox) {
@@ -134,7 +144,17 @@ __global__ __launch_bounds__(TW * TH) void denoise_filter_kernel(const float2* _
 #pragma unroll
         for (int u = 0; u <= 2 * F; ++u) P += H[(ly + u) * TW + lx];
         const int cnt = 3 * rtdn::patch_span(px, ox, F, width) * rtdn::patch_span(py, oy, F, rows);
-        const unsigned long long W = rtdn::weight(P, cnt);
+        unsigned long long W;
+        if (GUIDED && (oy | ox) != 0) {
+          const long long q = (long long)qy * width + qx;
+          rtdn::Feature fq;
+#pragma unroll
+          for (int j = 0; j < 3; ++j) fq.n[j] = guide.normal[3 * q + j], fq.a[j] = guide.albedo[3 * q + j];
+          fq.z = guide.depth[q];
+          W = rtdn::weight(P, cnt, rtdn::feature_x(fp, fq, guide.gains));
+        } else {
+          W = rtdn::weight(P, cnt);
+        }
         const int q_at = p_at + shift;
 #pragma unroll
         for (int j = 0; j < 3; ++j) num[j] += W * rtdn::q_of(lds[j * plane + q_at]);
@@ -149,29 +169,29 @@ __global__ __launch_bounds__(TW * TH) void denoise_filter_kernel(const float2* _
   if (gain) gain[p] = rtdn::gain(den);
 }
 
-template <int F, int TW, int TH>
+template <int F, int TW, int TH, bool GUIDED>
 hipError_t launch_filter(hipStream_t stream, const rt_denoise_params& p, const float2* mv, int rows, int width, uint8_t* out,
-                         float* gain) {
+                         float* gain, const rtdn::GuideView& guide) {
   const size_t HW = TW + 2 * (size_t)(p.search_radius + F), HH = TH + 2 * (size_t)(p.search_radius + F);
   const size_t lds = (6 * HW * HH + (size_t)(TW + 2 * F) * (TH + 2 * F) + (size_t)(TH + 2 * F) * TW) * sizeof(float);
   if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&denoise_filter_kernel<F, TW, TH>),
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&denoise_filter_kernel<F, TW, TH, GUIDED>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
   const dim3 grid((unsigned)((width + TW - 1) / TW), (unsigned)((rows + TH - 1) / TH));
-  hipLaunchKernelGGL((denoise_filter_kernel<F, TW, TH>), grid, dim3(TW * TH), lds, stream, mv, rows, width, p.search_radius,
-                     p.alpha, p.k * p.k, p.eps, out, gain);
+  hipLaunchKernelGGL((denoise_filter_kernel<F, TW, TH, GUIDED>), grid, dim3(TW * TH), lds, stream, mv, rows, width,
+                     p.search_radius, p.alpha, p.k * p.k, p.eps, out, gain, guide);
   return hipGetLastError();
 }
-template <int TW, int TH>
+template <int TW, int TH, bool GUIDED>
 hipError_t launch_filter_f(hipStream_t stream, const rt_denoise_params& p, const float2* mv, int rows, int width, uint8_t* out,
-                           float* gain) {
+                           float* gain, const rtdn::GuideView& guide) {
   switch (p.patch_radius) {
-    case 0: return launch_filter<0, TW, TH>(stream, p, mv, rows, width, out, gain);
-    case 1: return launch_filter<1, TW, TH>(stream, p, mv, rows, width, out, gain);
-    case 2: return launch_filter<2, TW, TH>(stream, p, mv, rows, width, out, gain);
-    default: return launch_filter<3, TW, TH>(stream, p, mv, rows, width, out, gain);
+    case 0: return launch_filter<0, TW, TH, GUIDED>(stream, p, mv, rows, width, out, gain, guide);
+    case 1: return launch_filter<1, TW, TH, GUIDED>(stream, p, mv, rows, width, out, gain, guide);
+    case 2: return launch_filter<2, TW, TH, GUIDED>(stream, p, mv, rows, width, out, gain, guide);
+    default: return launch_filter<3, TW, TH, GUIDED>(stream, p, mv, rows, width, out, gain, guide);
   }
 }
 
@@ -180,13 +200,14 @@ hipError_t launch_filter_f(hipStream_t stream, const rt_denoise_params& p, const
 namespace rtdn {
 
 hipError_t launch(hipStream_t stream, const uint32_t* s1, const unsigned long long* s2, const int32_t* tile_n, int n, int rows,
-                  int width, const rt_denoise_params& p, float2* mv, uint8_t* out, float* gain) {
+                  int width, const rt_denoise_params& p, float2* mv, uint8_t* out, float* gain, const GuideView* guide) {
   const long long n_values = 3LL * rows * width;
   hipLaunchKernelGGL(denoise_prepare_kernel, dim3((unsigned)((n_values + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, s1, s2,
                      tile_n, n, width, n_values, mv);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  return launch_filter_f<kTileW, kTileH>(stream, p, mv, rows, width, out, gain);
+  if (guide) return launch_filter_f<kTileW, kTileH, true>(stream, p, mv, rows, width, out, gain, *guide);
+  return launch_filter_f<kTileW, kTileH, false>(stream, p, mv, rows, width, out, gain, GuideView{});
 }
 
 }  // namespace rtdn

@@ -17,9 +17,9 @@ static_assert(__BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__, "the payload is read as
 namespace {
 
 // p1 / p2: the blob's S1 (u32) and S2 (u64) arrays, possibly unaligned; tile_n: n_t per noise tile (u8 pointer to
-// i32, possibly unaligned), or null with n for every pixel.
+// i32, possibly unaligned), or null with n for every pixel.  guide: the feature planes of the guided denoise, or null.
 int denoise_host(int64_t rows, int64_t width, const unsigned char* p1, const unsigned char* p2, const unsigned char* tile_n,
-                 int32_t n, const rt_denoise_params* prm, uint8_t* out, float* gain) {
+                 int32_t n, const rt_denoise_params* prm, const rtdn::GuideView* guide, uint8_t* out, float* gain) {
   const int64_t px_count = rows * width, tiles_x = (width + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
   std::vector<float> M((size_t)px_count * 3), V((size_t)px_count * 3);
   for (int64_t r = 0; r < rows; ++r)
@@ -67,8 +67,19 @@ int denoise_host(int64_t rows, int64_t width, const unsigned char* p1, const uns
           const int64_t P = sat[(size_t)((y1 + 1) * sw + x1 + 1)] - sat[(size_t)(y0 * sw + x1 + 1)] -
                             sat[(size_t)((y1 + 1) * sw + x0)] + sat[(size_t)(y0 * sw + x0)];
           const int32_t cnt = 3 * rtdn::patch_span((int32_t)x, ox, f, (int32_t)width) * rtdn::patch_span((int32_t)y, oy, f, (int32_t)rows);
-          const uint64_t W = rtdn::weight((int32_t)P, cnt);
           const size_t p = (size_t)(y * width + x), q = (size_t)(qy * width + qx);
+          uint64_t W;
+          if (guide && (oy | ox) != 0) {
+            rtdn::Feature fp, fq;
+            for (int j = 0; j < 3; ++j) {
+              fp.n[j] = guide->normal[3 * p + j], fp.a[j] = guide->albedo[3 * p + j];
+              fq.n[j] = guide->normal[3 * q + j], fq.a[j] = guide->albedo[3 * q + j];
+            }
+            fp.z = guide->depth[p], fq.z = guide->depth[q];
+            W = rtdn::weight((int32_t)P, cnt, rtdn::feature_x(fp, fq, guide->gains));
+          } else {
+            W = rtdn::weight((int32_t)P, cnt);
+          }
           for (int j = 0; j < 3; ++j) num[3 * p + j] += W * rtdn::q_of(M[3 * q + j]);
           den[p] += W;
         }
@@ -81,14 +92,57 @@ int denoise_host(int64_t rows, int64_t width, const unsigned char* p1, const uns
   return RT_OK;
 }
 
-// What both entry points check after their blob: the whole-image tiling, the parameters, the image pointer.
-int denoise_check(const rt_accum_info& i, const rt_denoise_params* prm, const uint8_t* out) {
+// What both entry points check after their blob: the whole-image tiling, the parameters, the image pointer, and
+// with planes their gains, pointers and size.
+int denoise_check(const rt_accum_info& i, const rt_denoise_params* prm, const rtdn::GuideView* guide, int32_t plane_width,
+                  int32_t plane_height, const uint8_t* out) {
   if (!out || !rtdn::params_ok(prm)) return RT_ERR_ARG;
   if (i.n_values != (int64_t)i.args.width * i.args.height * 3) return RT_ERR_ARG;  // a band tiling
+  if (guide && (!rtdn::guide_params_ok(&guide->gains) || !guide->normal || !guide->albedo || !guide->depth ||
+                plane_width != i.args.width || plane_height != i.args.height))
+    return RT_ERR_ARG;
   return RT_OK;
 }
 
 }  // namespace
+
+namespace rtdn {
+
+int monitor_blob(const void* blob, size_t n, const rt_denoise_params* prm, const GuideView* guide, int32_t plane_width,
+                 int32_t plane_height, uint8_t* out, float* gain) {
+  rt_accum_info i;
+  rt_denoise_params defaults;
+  if (!prm) rt_denoise_params_default(&defaults), prm = &defaults;
+  int rc = rt_noise_blob_info(blob, n, &i);
+  if (rc) return rc;
+  if ((rc = denoise_check(i, prm, guide, plane_width, plane_height, out))) return rc;
+  if (i.args.fb_count < 2) return RT_ERR_STATE;
+  const unsigned char* p2 = static_cast<const unsigned char*>(blob) + rtacc::kHeaderBytes;
+  const unsigned char* p1 = p2 + (size_t)i.n_values * sizeof(uint64_t);
+  return denoise_host(i.args.height, i.args.width, p1, p2, nullptr, i.args.fb_count, prm, guide, out, gain);
+}
+
+int adaptive_blob(const void* blob, size_t n, const rt_denoise_params* prm, const GuideView* guide, int32_t plane_width,
+                  int32_t plane_height, uint8_t* out, float* gain) {
+  rt_accum_info i;
+  rt_denoise_params defaults;
+  if (!prm) rt_denoise_params_default(&defaults), prm = &defaults;
+  int rc = rt_adaptive_blob_info(blob, n, &i);
+  if (rc) return rc;
+  if ((rc = denoise_check(i, prm, guide, plane_width, plane_height, out))) return rc;
+  const int64_t tiles_x = (i.args.width + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
+  const int64_t tiles_y = (i.args.height + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
+  const rtacc::AdaptLayout l = rtacc::adapt_layout((size_t)i.n_values, (size_t)(tiles_x * tiles_y));
+  const unsigned char* p = static_cast<const unsigned char*>(blob);
+  for (int64_t t = 0; t < tiles_x * tiles_y; ++t) {  // V divides by n_t - 1
+    int32_t nt;
+    memcpy(&nt, p + l.n_t + 4 * t, 4);
+    if (nt < 2) return RT_ERR_STATE;
+  }
+  return denoise_host(i.args.height, i.args.width, p + l.s1, p + l.s2, p + l.n_t, 0, prm, guide, out, gain);
+}
+
+}  // namespace rtdn
 
 extern "C" {
 
@@ -103,35 +157,11 @@ void rt_denoise_params_default(rt_denoise_params* p) {
 }
 
 int rt_denoise_monitor_blob(const void* blob, size_t n, const rt_denoise_params* prm, uint8_t* out, float* gain) {
-  rt_accum_info i;
-  rt_denoise_params defaults;
-  if (!prm) rt_denoise_params_default(&defaults), prm = &defaults;
-  int rc = rt_noise_blob_info(blob, n, &i);
-  if (rc) return rc;
-  if ((rc = denoise_check(i, prm, out))) return rc;
-  if (i.args.fb_count < 2) return RT_ERR_STATE;
-  const unsigned char* p2 = static_cast<const unsigned char*>(blob) + rtacc::kHeaderBytes;
-  const unsigned char* p1 = p2 + (size_t)i.n_values * sizeof(uint64_t);
-  return denoise_host(i.args.height, i.args.width, p1, p2, nullptr, i.args.fb_count, prm, out, gain);
+  return rtdn::monitor_blob(blob, n, prm, nullptr, 0, 0, out, gain);
 }
 
 int rt_denoise_adaptive_blob(const void* blob, size_t n, const rt_denoise_params* prm, uint8_t* out, float* gain) {
-  rt_accum_info i;
-  rt_denoise_params defaults;
-  if (!prm) rt_denoise_params_default(&defaults), prm = &defaults;
-  int rc = rt_adaptive_blob_info(blob, n, &i);
-  if (rc) return rc;
-  if ((rc = denoise_check(i, prm, out))) return rc;
-  const int64_t tiles_x = (i.args.width + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
-  const int64_t tiles_y = (i.args.height + rtacc::kNoiseTile - 1) / rtacc::kNoiseTile;
-  const rtacc::AdaptLayout l = rtacc::adapt_layout((size_t)i.n_values, (size_t)(tiles_x * tiles_y));
-  const unsigned char* p = static_cast<const unsigned char*>(blob);
-  for (int64_t t = 0; t < tiles_x * tiles_y; ++t) {  // V divides by n_t - 1
-    int32_t nt;
-    memcpy(&nt, p + l.n_t + 4 * t, 4);
-    if (nt < 2) return RT_ERR_STATE;
-  }
-  return denoise_host(i.args.height, i.args.width, p + l.s1, p + l.s2, p + l.n_t, 0, prm, out, gain);
+  return rtdn::adaptive_blob(blob, n, prm, nullptr, 0, 0, out, gain);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include "rt_denoise.h"
 #include "rt_denoise_math.h"
 #include "rt_devbuf.h"
+#include "rt_guide.h"
 #include "rt_quant.h"
 #include "rt_tile_list.h"
 
@@ -515,7 +516,7 @@ int image_out(AccumCore& k, uint8_t* out, int32_t png_order, const char* nomem, 
 // tile_n_dev at its noise tile's -- into image_out's image, and the gain beside it under the same conventions.
 // The (M, V) scratch lives for the call only.
 int denoise_out(AccumCore& k, const Moments& m, const int32_t* tile_n_dev, int n, Timer& timer, const rt_denoise_params* params,
-                uint8_t* out, float* gain, int32_t png_order) {
+                uint8_t* out, float* gain, int32_t png_order, const rtdn::GuideView* guide = nullptr) {
   rt_ctx* c = k.ctx;
   rt_denoise_params p;
   if (params) p = *params;
@@ -535,7 +536,7 @@ int denoise_out(AccumCore& k, const Moments& m, const int32_t* tile_n_dev, int n
     if (!mv.alloc(pixels * 3) || (gain_host && !gain_tmp.alloc(pixels))) return fail(c, RT_ERR_NOMEM, "hipMalloc denoise scratch");
     float* gain_dev = gain_host ? gain_tmp.get() : gain;
     HIPCHK(c, timer.start(stream));
-    HIPCHK(c, rtdn::launch(stream, m.s1.get(), m.s2.get(), tile_n_dev, n, m.grid.rows, m.grid.width, p, mv.get(), img, gain_dev));
+    HIPCHK(c, rtdn::launch(stream, m.s1.get(), m.s2.get(), tile_n_dev, n, m.grid.rows, m.grid.width, p, mv.get(), img, gain_dev, guide));
     HIPCHK(c, timer.stop(stream));
     if (gain_host) {
       if (png_order) gain_rows.resize(pixels);
@@ -549,6 +550,23 @@ int denoise_out(AccumCore& k, const Moments& m, const int32_t* tile_n_dev, int n
     const size_t w = (size_t)m.grid.width, h = (size_t)m.grid.rows;
     for (size_t j = 0; j < h; ++j) memcpy(gain + (h - 1 - j) * w, gain_rows.data() + j * w, w * sizeof(float));
   }
+  return RT_OK;
+}
+
+// rt_guide_denoise_monitor and rt_guide_denoise_adaptive: the guide's planes as the filter's view of them, after
+// the checks that are the guided call's own -- the gains, then that g has rendered planes of k's image size, on
+// k's device, of the scene with fingerprint scene_fp.
+int guide_view(AccumCore& k, uint64_t scene_fp, const rt_guide* g, const rt_guide_params* gparams, rtdn::GuideView* gv) {
+  rt_ctx* c = k.ctx;
+  if (gparams) gv->gains = *gparams;
+  else rt_guide_params_default(&gv->gains);
+  if (!rtdn::guide_params_ok(&gv->gains)) return fail(c, RT_ERR_ARG, "guided denoise: gains out of range");
+  const rtguide::View v = rtguide::view(g);
+  if (!v.width) return fail(c, RT_ERR_STATE, "guided denoise: the guide has rendered no planes");
+  if (v.width != k.args.width || v.height != k.args.height) return fail(c, RT_ERR_STATE, "guided denoise: the guide's planes have another size");
+  if (v.scene_fp != scene_fp) return fail(c, RT_ERR_STATE, "guided denoise: the guide belongs to another scene");
+  if (v.device != view(c).device) return fail(c, RT_ERR_STATE, "guided denoise: the guide lives on another device");
+  gv->normal = v.normal, gv->albedo = v.albedo, gv->depth = v.depth;
   return RT_OK;
 }
 
@@ -868,6 +886,17 @@ int rt_denoise_monitor(rt_noise* nm, const rt_denoise_params* params, uint8_t* o
   return denoise_out(*nm->acc, nm->m, nullptr, nm->fbs, nm->denoise_timer, params, out, gain, png_order);
 }
 float rt_denoise_monitor_last_ms(const rt_noise* nm) { return nm ? nm->denoise_timer.ms() : 0.0f; }
+
+int rt_guide_denoise_monitor(rt_noise* nm, rt_guide* g, const rt_denoise_params* params, const rt_guide_params* gparams,
+                             uint8_t* out, float* gain, int32_t png_order) {
+  if (!nm || !g) return RT_ERR_ARG;
+  if (!nm->acc) return RT_ERR_STATE;  // detached
+  rtdn::GuideView gv;
+  const int rc = guide_view(*nm->acc, nm->acc->scene_fp, g, gparams, &gv);
+  if (rc) return rc;
+  if (nm->fbs < 2) return fail(nm->acc->ctx, RT_ERR_STATE, "denoise needs at least 2 frame buffers");
+  return denoise_out(*nm->acc, nm->m, nullptr, nm->fbs, nm->denoise_timer, params, out, gain, png_order, &gv);
+}
 
 int rt_noise_save(rt_noise* nm, void* blob, size_t cap, size_t* need) {
   if (!nm) return RT_ERR_ARG;
@@ -1382,6 +1411,17 @@ int rt_denoise_adaptive(rt_adapt* ad, const rt_denoise_params* params, uint8_t* 
   return denoise_out(*ad, ad->m, ad->tile_n.get(), 0, ad->denoise_timer, params, out, gain, png_order);
 }
 float rt_denoise_adaptive_last_ms(const rt_adapt* ad) { return ad ? ad->denoise_timer.ms() : 0.0f; }
+
+int rt_guide_denoise_adaptive(rt_adapt* ad, rt_guide* g, const rt_denoise_params* params, const rt_guide_params* gparams,
+                              uint8_t* out, float* gain, int32_t png_order) {
+  if (!ad || !g) return RT_ERR_ARG;
+  rtdn::GuideView gv;
+  const int rc = guide_view(*ad, ad->scene_fp, g, gparams, &gv);
+  if (rc) return rc;
+  for (int32_t n : ad->n_t)  // V divides by n_t - 1
+    if (n < 2) return fail(ad->ctx, RT_ERR_STATE, "denoise needs at least 2 frame buffers in every tile");
+  return denoise_out(*ad, ad->m, ad->tile_n.get(), 0, ad->denoise_timer, params, out, gain, png_order, &gv);
+}
 
 float rt_adapt_last_add_ms(const rt_adapt* ad) { return ad ? ad->add_timer.ms() : 0.0f; }
 float rt_adapt_last_retire_ms(const rt_adapt* ad) { return ad ? ad->retire_timer.ms() : 0.0f; }
