@@ -3,8 +3,9 @@
 // The product library (raytracing_gpu_amd/_build.py) defines nothing here: every hook below is an
 // empty macro, the kernels carry no timing code and the library reads no environment variable.
 // A diagnostic build sets -DRT_DIAG=<bits> (scripts/build_ab.sh NAME src -DRT_DIAG=...):
-//   1  per-wave counts of traversal-loop iterations, lane steps, shading phases, loop trips and the
-//      traversal's leaf passes with their lanes (printed to stderr after each launch)
+//   1  per-wave counts of traversal-loop iterations, lane steps, shading phases, loop trips, the
+//      traversal's leaf passes with their lanes, and the stepwise kernel's refills: passes that enter
+//      one, lanes refilled, chunk claims (printed to stderr after each launch)
 //   2  per-wave cycle shares of the loop's phases: s_memtime stamps, appended to $RT_STAMPS_OUT
 //      (scripts/diag_stamps.py)
 //   4  per-wave start / work-exhausted / end times (s_memrealtime), written to $RT_WAVE_TIMES_OUT
@@ -23,15 +24,17 @@
 #if RT_DIAG & 1
 // 0 traversal-loop iterations, 1 lanes stepping in them, 2 shading phases, 3 loop trips,
 // 4 / 5 leaf passes entered first (a step's first pass, or the first pass of a vote) and the lanes
-// testing a leaf in them, 6 / 7 the same for the passes that follow it (a lane's second leaf)
-constexpr int kStepCounts = 8;
+// testing a leaf in them, 6 / 7 the same for the passes that follow it (a lane's second leaf),
+// 8 / 9 render_step_kernel's shading passes that enter the refill and the lanes without an item in
+// them, 10 chunks claimed from the work counter
+constexpr int kStepCounts = 11;
 __device__ unsigned long long rt_diag_steps[kStepCounts];
 __shared__ unsigned long long rt_diag_steps_acc[16][kStepCounts];
 __device__ __forceinline__ void rt_step_count(int k) {  // one count per wave (first active lane)
   const unsigned long long act = __ballot(1);
   if ((int)__lane_id() == __ffsll((long long)act) - 1) {
     rt_diag_steps_acc[threadIdx.x >> 6][k] += 1;
-    if (k == 0 || k == 4 || k == 6) rt_diag_steps_acc[threadIdx.x >> 6][k + 1] += __popcll(act);
+    if (k == 0 || k == 4 || k == 6 || k == 8) rt_diag_steps_acc[threadIdx.x >> 6][k + 1] += __popcll(act);
   }
 }
 #define RT_STEP_COUNT(k) rt_step_count(k)
@@ -49,8 +52,9 @@ __device__ __forceinline__ void rt_step_count(int k) {  // one count per wave (f
     unsigned long long h_[kStepCounts];                                                                     \
     (void)hipMemcpyFromSymbol(h_, HIP_SYMBOL(rt_diag_steps), sizeof(h_));                                   \
     fprintf(stderr, "RT_STEP_DIAG var=%d trav_wave_iters=%llu trav_lane_steps=%llu shade_phases=%llu trips=%llu" \
-            " leaf_first=%llu leaf_first_lanes=%llu leaf_more=%llu leaf_more_lanes=%llu\n",                 \
-            var, h_[0], h_[1], h_[2], h_[3], h_[4], h_[5], h_[6], h_[7]);                                    \
+            " leaf_first=%llu leaf_first_lanes=%llu leaf_more=%llu leaf_more_lanes=%llu"                    \
+            " refill_passes=%llu refill_lanes=%llu chunk_claims=%llu\n",                                    \
+            var, h_[0], h_[1], h_[2], h_[3], h_[4], h_[5], h_[6], h_[7], h_[8], h_[9], h_[10]);              \
   } while (0)
 #else
 #define RT_STEP_COUNT(k)
@@ -61,10 +65,11 @@ __device__ __forceinline__ void rt_step_count(int k) {  // one count per wave (f
 #endif
 
 // ---------------------------------------------------------------- 2: phase stamps
-// Phase = code run after the stamp: 0 head, 1 camera, 2 world glue, 3 node tests, 4 primitive tests,
-// 5 validation, 6 scatter, 7 one stamp (a back-to-back pair measures the stamp itself).
+// Phase = code run after the stamp: 0 head (render_step_kernel: the sample end), 1 camera, 2 world glue,
+// 3 node tests, 4 primitive tests, 5 validation, 6 scatter, 7 one stamp (a back-to-back pair measures
+// the stamp itself), 8 render_step_kernel's refill.
 #if RT_DIAG & 2
-constexpr int kStampPhases = 8;
+constexpr int kStampPhases = 9;
 __device__ unsigned long long rt_diag_stamps[kStampPhases];
 __shared__ unsigned long long rt_stamp_acc[16][kStampPhases + 2];
 __device__ __forceinline__ void rt_stamp(int ph) {

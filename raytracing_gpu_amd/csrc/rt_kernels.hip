@@ -1976,6 +1976,21 @@ constexpr int kRefill = 4;
 // 18 741 / 18 659 Mrays/s; profiles/r05/refill_ab.txt)
 template <int F>
 constexpr int step_refill() { return (F & F_TRI) != 0 ? 4 : 1; }
+// render_step_kernel's item pool (the sphere variants that park nothing): a wave decodes the kChunk
+// positions of a claim at once, lane L position chunk + L with every lane active -- perm, row_q, the
+// H3 slot and the slot's RNG state -- and keeps the result in registers; a refill then hands the next
+// entries to the lanes without an item by cross-lane reads.  The refill runs in every second shading
+// pass for four or five lanes (step_refill 1; C2: 46 % of the passes, 4.5 lanes), so the decode's
+// divisions and its three dependent loads are paid once per kChunk items by a full wave instead (C2
+// 2.6 % faster).  The mesh variants (step_refill 4; C4 measured 4.6 % slower with the
+// pool) and the LDS-locker ones keep the per-lane decode, as do split launches and launches too large
+// for the pool's packed words (pool_fits).  -DRT_STEP_POOL=0 builds every variant with the per-lane
+// decode (A/B, diagnostics).
+#ifndef RT_STEP_POOL
+#define RT_STEP_POOL 1
+#endif
+template <int F>
+constexpr bool step_pools() { return RT_STEP_POOL != 0 && (F & F_STEP) != 0 && (F & (F_TRI | F_WORLD)) == 0; }
 constexpr int kShadeMin = 60;  // render_step_kernel: default shading-phase threshold
 constexpr int kShadeMinMesh = 48;  // ... for triangle-mesh variants (round 5, with step_refill 4: C4 at
                                    // 36 / 40 / 44 / 48 / 52 / 56 / 60: 18 845 / 18 971 / 19 048 / 19 079 /
@@ -2024,6 +2039,7 @@ __device__ __forceinline__ unsigned long long claim_items(unsigned long long* wo
   const unsigned old_left = chunk_left;
   unsigned long long fresh = 0;
   if (old_left < nidle) {
+    RT_STEP_COUNT(10);
     const int leader = __ffsll((long long)idle) - 1;
     if ((int)__lane_id() == leader) fresh = atomicAdd(work, (unsigned long long)kChunk);
     fresh = __shfl(fresh, leader, 64);
@@ -2423,6 +2439,15 @@ void render_step_kernel(const RenderParams P) {
   const rt_camera& C = S.cam;
   unsigned long long chunk_base = 0;  // wave-uniform: next unclaimed item of the wave's chunk
   unsigned chunk_left = 0;
+  // The item pool (step_pools): lane L holds the decoded entry of position L of the wave's chunk -- the
+  // item, (f, i) and (r, j) as 16-bit halves, the slot's six state words; the last chunk_left entries
+  // (lanes kChunk - chunk_left on, positions chunk_base on) are not handed out yet.
+  constexpr bool POOL = step_pools<F>();
+  static_assert(!POOL || kChunk == 64, "the item pool holds one entry per lane");
+  uint32_t pl_item = 0, pl_fi = 0, pl_rj = 0, pl_s0 = 0, pl_s1 = 0, pl_s2 = 0, pl_s3 = 0, pl_s4 = 0, pl_s5 = 0;
+  // what the packed words hold; anything else decodes per lane (wave-uniform, constant over the launch)
+  const bool pool_fits = POOL && P.split_mode == 0 && P.total_items <= 0xffffffffull && P.W <= 65536 && P.H <= 65536 &&
+                         P.fb_count <= 65536;
   RT_WAVE_T0();
 
   for (;;) {
@@ -2559,13 +2584,87 @@ void render_step_kernel(const RenderParams P) {
         }
         mode = 0;
       }
-      RT_STAMP(0);
+      RT_STAMP(8);
       // ---- refill lanes without an item from the wave's chunk of the work counter (one atomic
       // per kChunk items: a single counter serialises its atomics in L2)
       const unsigned long long idle = __ballot(item < 0 && !done);
-      if (idle != 0 && (__popcll(idle) >= step_refill<F>() || __ballot(item >= 0) == 0)) {
+      if (POOL && pool_fits && idle != 0) {  // (step_refill 1: at every idle lane)
+        static_assert(!POOL || step_refill<F>() == 1, "the pooled refill runs whenever a lane is idle");
+        // From the pool: the lane of rank k among the idle ones takes position chunk_base + k, as
+        // claim_items hands them out.  Every lane runs the cross-lane reads (wave-uniform control flow:
+        // ds_bpermute returns 0 from a lane that is off); at most two rounds, the second after a claim.
+        bool want = item < 0 && !done;
+        if (want) {
+          RT_STEP_COUNT(8);
+        }
+        unsigned rk = lane_rank(idle);
+        unsigned need = (unsigned)__popcll(idle);
+        for (;;) {
+          if (chunk_left == 0) {  // claim a chunk and decode it, one position per lane
+            RT_STEP_COUNT(10);
+            unsigned long long got = 0;
+            if (lane == 0) got = atomicAdd(P.work, (unsigned long long)kChunk);
+            chunk_base = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(got >> 32)) << 32) |
+                         __builtin_amdgcn_readfirstlane((unsigned)got);
+            chunk_left = kChunk;
+            const unsigned long long pos = chunk_base + lane;
+            if (pos < P.total_items) {
+              const long long it = P.perm ? (long long)P.perm[pos] : (long long)pos;
+              const long long per_row = P.per_row;  // same item order as render_kernel
+              const int qi = (int)(it / per_row);
+              const long long rem = it - (long long)qi * per_row;
+              const int2 rj = P.row_q[qi * P.pstep];
+              const int pf = (int)(rem / P.W);
+              const int pi = (int)(rem - (long long)pf * P.W) * P.pstep;
+              const long long id = P.fb_first + pf;
+              const long long p = (long long)rj.y * P.W + pi;
+              const long long slot = ((id + 1) * p + id + 1) % P.npix;  // render.h:101 (H3)
+              const uint4* st = P.states + 2 * slot;
+              const uint4 s0 = st[0], s1 = st[1];
+              pl_item = (uint32_t)it;
+              pl_fi = ((uint32_t)pf << 16) | (uint32_t)pi;
+              pl_rj = ((uint32_t)rj.x << 16) | (uint32_t)rj.y;
+              pl_s0 = s0.x; pl_s1 = s0.y; pl_s2 = s0.z; pl_s3 = s0.w; pl_s4 = s1.x; pl_s5 = s1.y;
+            }
+          }
+          const unsigned take = need < chunk_left ? need : chunk_left;
+          const int src = (int)(kChunk - chunk_left + rk);
+          const uint32_t g_item = __shfl(pl_item, src, 64), g_fi = __shfl(pl_fi, src, 64), g_rj = __shfl(pl_rj, src, 64);
+          const uint32_t g0 = __shfl(pl_s0, src, 64), g1 = __shfl(pl_s1, src, 64), g2 = __shfl(pl_s2, src, 64);
+          const uint32_t g3 = __shfl(pl_s3, src, 64), g4 = __shfl(pl_s4, src, 64), g5 = __shfl(pl_s5, src, 64);
+          if (want && rk < take) {
+            const unsigned long long pos = chunk_base + rk;
+            if (pos >= P.total_items) {
+              done = true;
+              RT_WAVE_EXHAUSTED();
+            } else {
+              item = (long long)g_item;
+              lng = pos < P.n_long ? 1 : 0;
+              f = (int)(g_fi >> 16);
+              i = (int)(g_fi & 0xffffu);
+              r = (int)(g_rj >> 16);
+              j = (int)(g_rj & 0xffffu);
+              loc.d = g0; loc.v[0] = g1; loc.v[1] = g2; loc.v[2] = g3; loc.v[3] = g4; loc.v[4] = g5;
+              s = 0;
+              s_end_r = P.spp;
+              fresh = 1;
+              depth = 0;
+              item_segs = 0;
+              col_r = mk(0, 0, 0);
+            }
+            want = false;
+          }
+          rk -= take;
+          chunk_base += take;
+          chunk_left -= take;
+          need -= take;
+          if (need == 0) break;
+        }
+      }
+      if ((!POOL || !pool_fits) && idle != 0 && (__popcll(idle) >= step_refill<F>() || __ballot(item >= 0) == 0)) {
         const unsigned long long mine = claim_items(P.work, idle, chunk_base, chunk_left);
         if (item < 0 && !done) {
+          RT_STEP_COUNT(8);
           if (mine >= P.total_items) {
             done = true;
             RT_WAVE_EXHAUSTED();

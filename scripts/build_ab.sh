@@ -13,5 +13,6 @@ cp "$src" "$tmp/raytracing_gpu_amd/csrc/rt_kernels.hip"
 cd "$tmp/raytracing_gpu_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off \
   -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -fno-slp-vectorize "$@" -o "$root/build/ab/lib$name.so" \
-  rt_kernels.hip rt_progressive.hip rt_scene.cpp rt_obj.cpp rt_image.cpp rt_accum_blob.cpp rt_noise_blob.cpp rt_adapt_blob.cpp rt_validate.cpp
+  rt_kernels.hip rt_progressive.hip rt_denoise.hip rt_guide.hip rt_scene.cpp rt_obj.cpp rt_image.cpp rt_accum_blob.cpp \
+  rt_noise_blob.cpp rt_adapt_blob.cpp rt_denoise_blob.cpp rt_guide_host.cpp rt_validate.cpp
 rm -rf "$tmp"
