@@ -18,9 +18,10 @@ EXAMPLES = os.path.join(ROOT, "examples")
 RT_MAIN = os.path.join(EXAMPLES, "bin", "rt_main")
 
 HIP_SOURCES = ["rt_kernels.hip", "rt_progressive.hip", "rt_denoise.hip", "rt_guide.hip", "rt_scene.cpp", "rt_obj.cpp", "rt_image.cpp",
-               "rt_accum_blob.cpp", "rt_noise_blob.cpp", "rt_adapt_blob.cpp", "rt_denoise_blob.cpp", "rt_guide_host.cpp", "rt_validate.cpp"]
+               "rt_accum_blob.cpp", "rt_noise_blob.cpp", "rt_adapt_blob.cpp", "rt_denoise_blob.cpp", "rt_guide_host.cpp", "rt_validate.cpp",
+               "rt_scene_prep.cpp"]
 # every header of csrc/ (rt_diag.h included): an edit to any of them rebuilds the library and changes
-# kernel_build_id() (tests/test_build_cpu.py checks that each local #include is covered)
+# kernel_build_id() (tests/test_oracle_cpu.py checks that each local #include is covered)
 HIP_DEPS = HIP_SOURCES + sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
 # -ffp-contract=off: no FMA contraction anywhere, so every float op rounds like the reference's
 # C++ source and like the CPU oracle; fp32 div/sqrt correctly rounded (IEEE) on the device.

@@ -2,6 +2,8 @@
 // render side.  Everything here is defined in rt_kernels.hip; struct rt_ctx itself stays private to that
 // file.  Hidden visibility: the library exports what include/rt_hip.h declares and none of these.
 // The owned device buffers of both files (DevBuf, Staged) are rt_devbuf.h, over device_ptr below.
+// (The other internal interface of rt_kernels.hip is rt_scene_prep.h: the host-only scene preparation
+// behind rt_scene_upload and the constants it shares with the kernels.)
 #ifndef RT_CTX_INTERNAL_H
 #define RT_CTX_INTERNAL_H
 

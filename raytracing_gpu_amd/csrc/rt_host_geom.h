@@ -1,5 +1,5 @@
 // rt_host_geom.h — host-side primitive bounding boxes (sphere.h:75-78, moving_sphere.h:61-66,
-// aarect.h bounding_box, triangle.h:46-98), shared by the scene library and rt_scene_upload.
+// aarect.h bounding_box, triangle.h:46-98), shared by the scene library and scene preparation (rt_scene_prep.cpp).
 #pragma once
 
 #include <algorithm>
