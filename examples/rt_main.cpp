@@ -44,6 +44,9 @@
 //                           the shipped gains) over the planes of an rt_guide of the scene
 //     --aov PREFIX          write PREFIX_normal.ppm and PREFIX_albedo.ppm: the noise-free normal and albedo
 //                           images of the camera's centre rays (rt_guide_render, rt_guide_image)
+//     --guide-samples S     with --guided or --aov: the planes are averages of S rays per pixel spread over the
+//                           pixel, the lens and the shutter (rt_aov_render with the other defaults); --aov then
+//                           also writes PREFIX_coverage.ppm, the share of a pixel's rays that hit, in grey
 //
 // Writes OUT.ppm (binary P6, top row first) and one JSON line per draw on stdout.  Files written
 // more than once go to a temporary name first and are renamed into place.
@@ -318,7 +321,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: rt_main SCENE WIDTH SPP_PER_FB NO_FB OUT.ppm [--devices 0,1] [--gather rccl|host] "
                     "[--band-rows B] [--repeat K] [--depth D] [--height H] [--obj PATH] [--tex PATH] [--progressive K] [--checkpoint FILE] "
                     "[--until-noise T [--noisy-fraction F]] [--adaptive K --until-noise T [--max-above M] [--min-fbs F] "
-                    "[--adaptive-checkpoint FILE] [--dilate R] [--reopen]] [--denoise OUT2.ppm [--guided]] [--aov PREFIX]\n");
+                    "[--adaptive-checkpoint FILE] [--dilate R] [--reopen]] [--denoise OUT2.ppm [--guided]] [--aov PREFIX] [--guide-samples S]\n");
     return 2;
   }
   const char* name = argv[1];
@@ -330,7 +333,8 @@ int main(int argc, char** argv) {
   std::vector<int> devices;
   int gather = RT_GATHER_RCCL, band_rows = 4, repeat = 1;
   const char *obj_path = nullptr, *tex_path = nullptr, *ckpt_path = nullptr, *adaptive_ckpt = nullptr, *denoised = nullptr, *aov = nullptr;
-  bool guided = false;
+  bool guided = false, have_guide_samples = false;
+  int guide_samples = 0;
   int dilate = 0;
   bool reopen = false, have_resume_opts = false;
   int height = 0;
@@ -362,6 +366,7 @@ int main(int argc, char** argv) {
     else if (a == "--denoise") denoised = v, ++k;
     else if (a == "--guided") guided = true;
     else if (a == "--aov") aov = v, ++k;
+    else if (a == "--guide-samples") have_guide_samples = true, guide_samples = atoi(v), ++k;
     else if (a == "--noisy-fraction") have_fraction = true, noisy_fraction = atof(v), ++k;
     else return die("unknown option", argv[k]);
   }
@@ -382,6 +387,8 @@ int main(int argc, char** argv) {
   if (have_fraction && !until_noise) return die("--noisy-fraction", "needs --until-noise T");
   if (denoised && !have_adaptive && progressive <= 0) return die("--denoise", "needs --progressive K or --adaptive K");
   if (guided && !denoised) return die("--guided", "needs --denoise OUT2.ppm");
+  if (have_guide_samples && !guided && !aov) return die("--guide-samples", "needs --guided or --aov PREFIX");
+  if (have_guide_samples && (guide_samples < 1 || guide_samples > 256)) return die("--guide-samples", "S must be 1..256");
   if ((guided || aov) && !devices.empty()) return die("--guided / --aov", "one GPU only (no --devices)");
   if (denoised && s.no_fb > 32768) return die("--denoise", "a noise monitor accepts at most 32768 frame buffers");
   if (until_noise && s.no_fb > 32768) return die("--until-noise", "a noise monitor accepts at most 32768 frame buffers");
@@ -446,7 +453,14 @@ int main(int argc, char** argv) {
   rt_guide* guide = nullptr;
   if (guided || aov) {  // the feature planes of the camera's centre rays, from the guide's own copy of the scene
     if (rt_guide_create(soa, 0, &guide)) return die("rt_guide_create", name);
-    if (rt_guide_render(guide, a.width, a.height)) return die("rt_guide_render", name);
+    if (have_guide_samples) {  // ... or of S rays per pixel, averaged
+      rt_aov_params ap;
+      rt_aov_params_default(&ap);
+      ap.samples = guide_samples;
+      if (rt_aov_render(guide, a.width, a.height, &ap)) return die("rt_aov_render", name);
+    } else if (rt_guide_render(guide, a.width, a.height)) {
+      return die("rt_guide_render", name);
+    }
     if (guided) g_guide = guide;
     char head[64];
     snprintf(head, sizeof(head), "P6\n%d %d\n255\n", a.width, a.height);
@@ -455,7 +469,19 @@ int main(int argc, char** argv) {
       if (rt_guide_image(guide, which, png.data(), 1)) return die("rt_guide_image", path.c_str());
       if (!write_file(path, head, png.data(), png.size())) return die("write", path.c_str());
     }
-    if (aov) printf("{\"aov\": \"%s\", \"guide_ms\": %.3f}\n", aov, rt_guide_last_ms(guide));
+    if (aov && have_guide_samples) {  // quant(coverage) as write_frame_buffer quantises (color.h:40-44), in grey
+      const std::string path = std::string(aov) + "_coverage.ppm";
+      std::vector<float> cov((size_t)a.width * a.height);
+      if (rt_aov_coverage(guide, cov.data(), 1)) return die("rt_aov_coverage", path.c_str());
+      for (size_t p = 0; p < cov.size(); ++p) {
+        const float r = std::sqrt(cov[p]);
+        png[3 * p] = png[3 * p + 1] = png[3 * p + 2] = (uint8_t)(int)(256.0f * (r > 0.999f ? 0.999f : r));
+      }
+      if (!write_file(path, head, png.data(), png.size())) return die("write", path.c_str());
+      printf("{\"aov\": \"%s\", \"guide_ms\": %.3f, \"guide_samples\": %d}\n", aov, rt_aov_last_ms(guide), guide_samples);
+    } else if (aov) {
+      printf("{\"aov\": \"%s\", \"guide_ms\": %.3f}\n", aov, rt_guide_last_ms(guide));
+    }
   }
   if (have_adaptive) {
     if (!ctx) return die("--adaptive", "one GPU only (no --devices)");

@@ -791,6 +791,77 @@ int rt_guide_denoise_adaptive_blob(const void* blob, size_t n, const rt_denoise_
                                    const float* normal, const float* albedo, const float* depth, int32_t plane_width,
                                    int32_t plane_height, uint8_t* out, float* gain);
 
+/* ------------------------------------------------------------------ averaged feature planes */
+/* A guide's planes from several rays per pixel, spread over the pixel's footprint, the lens and the shutter, and
+ * averaged: normal, albedo and depth images that line up with a picture that has antialiased silhouettes, a depth
+ * of field and motion blur, where the centre ray's are sharp.  The rays are the guide's own (no render kernel is
+ * involved), the averages go into the guide's planes, so the planes, image and guided-denoise calls above work on
+ * them unchanged.  (A family of its own because the guide's is closed.)
+ *
+ * Everything is in float, one correctly rounded operation per operator, left to right, unless it says double.
+ *
+ * The pattern.  Sample s of S = samples is the same for every pixel (the planes are smooth, not noisy).  With P
+ * the smallest power of two >= S and rev2 the reversal of s in log2 P bits:
+ *
+ *   du = (float)(2 s + 1) / (float)(2 S)
+ *   dv = (float)(2 rev2 + 1) / (float)(2 P)                  footprint = 0: du = dv = 0.5f
+ *
+ * Lens points are the first S accepted candidates k = 1, 2, ... of a rejection walk in double, kept in order:
+ *
+ *   x = 2.0 (rev3 / 59049.0) - 1.0                           rev3: k's 10 base-3 digits reversed
+ *   y = 2.0 (rev5 / 78125.0) - 1.0                           rev5: k's 7 base-5 digits reversed
+ *   accepted when x x + y y <= 1.0;  lx = (float)x, ly = (float)y         lens = 0: lx = ly = 0
+ *
+ *   f = (float)(rev7 / 16807.0)   in double, rev7: s's 5 base-7 digits reversed       shutter = 0: f = 0.5f
+ *
+ * The ray of pixel (i, j), j = 0 the bottom row, of a W x H image for sample s (render.h:105-106 with the pattern
+ * in place of the random numbers, then camera.h:49-57 in the reference's order):
+ *
+ *   su = ((float)i + du) / (float)W;   sv = ((float)j + dv) / (float)H
+ *   rd = (lens_radius lx, lens_radius ly);   offset = rd.x u + rd.y v
+ *   origin    = origin + offset
+ *   direction = lower_left + su horizontal + sv vertical - origin - offset
+ *   time      = time0 + f (time1 - time0)
+ *
+ * With lens = 0 no offset is formed, added or subtracted: the ray is the centre pass's own expression at
+ * (su, sv) from the camera's origin.
+ *
+ * The average.  Every ray is cast as the guide casts any ray (a miss gives t = 0, n = 0, albedo = background).
+ * The sums start as sample 0's values, not as zero plus them (the sign of a zero survives), and take samples
+ * 1 .. S - 1 in order:
+ *
+ *   normal   = sum of n / (float)S          over all samples, as cast returns them (not renormalised)
+ *   albedo   = sum of albedo / (float)S     over all samples
+ *   depth    = sum of t over the hits / (float)hits,  0 with no hit
+ *   coverage = (float)hits / (float)S
+ *   prim     = the primitive of the hit of lowest s,  -1 with no hit
+ *
+ * samples = 1 with lens = 0 and shutter = 0 is therefore the centre pass, bit for bit (du = dv = 0.5f whatever
+ * footprint says).  The pattern and the per-pixel loop are stated once, in csrc/rt_aov.h, for both halves. */
+typedef struct rt_aov_params {
+  int32_t samples;    /* 1..256 */
+  int32_t lens;       /* 0 or 1: sample the lens (a camera with lens_radius 0 is unaffected) */
+  int32_t footprint;  /* 0 or 1: sample the pixel's area */
+  int32_t shutter;    /* 0 or 1: sample the shutter interval */
+} rt_aov_params;      /* 16 bytes */
+/* 16 samples, every switch 1. */
+void rt_aov_params_default(rt_aov_params* p);
+/* Host only: the table of p, out[samples][5] = du, dv, lx, ly, f.  RT_ERR_ARG for a null out, samples outside
+ * 1..256 or a switch that is neither 0 nor 1 (so everywhere below); p = NULL takes the defaults. */
+int rt_aov_pattern(const rt_aov_params* p, float* out);
+/* The averaged planes of a width x height image in place of the guide's planes (the centre pass's limits on width
+ * and height), with a coverage plane [height][width] beside them; kept until the next render of either kind. */
+int rt_aov_render(rt_guide* g, int32_t width, int32_t height, const rt_aov_params* p);
+/* The coverage plane, with the pointer and png_order conventions of the planes call (out may be NULL).
+ * RT_ERR_STATE unless the guide's current planes came from the averaged pass: a later centre pass drops it. */
+int rt_aov_coverage(rt_guide* g, float* out, int32_t png_order);
+/* Host only (no GPU; csrc/rt_guide_host.cpp): the same planes from the same code.  Host pointers, each may be
+ * NULL, row 0 the bottom row. */
+int rt_aov_render_host(const rt_scene_soa* scene, int32_t width, int32_t height, const rt_aov_params* p,
+                       float* normal, float* albedo, float* depth, int32_t* prim, float* coverage);
+/* Device time in ms of the last averaged pass's kernel; 0 before one. */
+float rt_aov_last_ms(const rt_guide* g);
+
 /* ------------------------------------------------------------------ host scene library */
 /* Builds one of the reference scenes (scenes.h) on the host: "basic", "first", "big1" (alias
  * "random"), "two_spheres", "two_perlin", "cornell", "cornell_smoke", "triangle", "triangles",

@@ -201,6 +201,14 @@ class rt_guide_params(ctypes.Structure):
         return {"normal_gain": float(self.normal_gain), "albedo_gain": float(self.albedo_gain), "depth_gain": float(self.depth_gain)}
 
 
+class rt_aov_params(ctypes.Structure):
+    """include/rt_hip.h rt_aov_params (16 bytes)."""
+    _fields_ = [("samples", c_int32), ("lens", c_int32), ("footprint", c_int32), ("shutter", c_int32)]
+
+    def as_dict(self) -> dict:
+        return {"samples": int(self.samples), "lens": int(self.lens), "footprint": int(self.footprint), "shutter": int(self.shutter)}
+
+
 # Every entry point of include/rt_hip.h: name -> (restype, argtypes)
 ABI = {
     "rt_ctx_create": (c_int, [c_int, POINTER(c_void_p)]),
@@ -293,6 +301,13 @@ ABI = {
                                               c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "rt_guide_denoise_adaptive_blob": (c_int, [c_void_p, c_size_t, POINTER(rt_denoise_params), POINTER(rt_guide_params), c_void_p,
                                                c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "rt_aov_params_default": (None, [POINTER(rt_aov_params)]),
+    "rt_aov_pattern": (c_int, [POINTER(rt_aov_params), c_void_p]),
+    "rt_aov_render": (c_int, [c_void_p, c_int32, c_int32, POINTER(rt_aov_params)]),
+    "rt_aov_coverage": (c_int, [c_void_p, c_void_p, c_int32]),
+    "rt_aov_render_host": (c_int, [POINTER(rt_scene_soa), c_int32, c_int32, POINTER(rt_aov_params), c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "rt_aov_last_ms": (c_float, [c_void_p]),
     "rt_scene_build": (c_int, [c_char_p, POINTER(c_void_p)]),
     "rt_scene_build_ex": (c_int, [c_char_p, c_void_p, POINTER(c_void_p)]),
     "rt_obj_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
@@ -375,6 +390,34 @@ def guide_params(params=None, **kw) -> rt_guide_params:
             raise TypeError(f"rt_guide_params has no field {k!r}")
         setattr(p, k, v)
     return p
+
+
+def aov_params(params=None, **kw) -> rt_aov_params:
+    """The sample pattern of the averaged feature planes (include/rt_hip.h): the shipped defaults, or a copy of
+    params (an rt_aov_params, a dict of its fields or None for the defaults), with the fields of kw set; a switch
+    may be a bool."""
+    p = rt_aov_params()
+    if isinstance(params, rt_aov_params):
+        ctypes.memmove(ctypes.byref(p), ctypes.byref(params), ctypes.sizeof(p))
+    else:
+        lib().rt_aov_params_default(ctypes.byref(p))
+        if isinstance(params, dict):
+            kw = {**params, **kw}
+    for k, v in kw.items():
+        if k not in ("samples", "lens", "footprint", "shutter"):
+            raise TypeError(f"rt_aov_params has no field {k!r}")
+        setattr(p, k, int(v))
+    return p
+
+
+def aov_pattern(params=None, **kw) -> np.ndarray:
+    """The (samples, 5) float32 table du, dv, lx, ly, f of aov_params(params, **kw) (rt_aov_pattern: host only)."""
+    p = aov_params(params, **kw)
+    out = np.zeros((max(0, min(int(p.samples), 256)), 5), np.float32)
+    rc = lib().rt_aov_pattern(ctypes.byref(p), out.ctypes.data)
+    if rc != 0:
+        raise RtError(f"rt_aov_pattern failed ({rc})", rc)
+    return out
 
 
 def _guided(fn, guide, guide_params_):
@@ -1110,11 +1153,23 @@ class Guide:
         """cast() between caller memory (device or host addresses)."""
         self._check(lib().rt_guide_cast(self._h, c_void_p(rays_ptr), n, c_void_p(out_ptr)), "rt_guide_cast")
 
-    def render(self, width: int, height: int) -> "Guide":
-        """The centre ray of every pixel into the guide's planes."""
-        self._check(lib().rt_guide_render(self._h, width, height), "rt_guide_render")
+    def render(self, width: int, height: int, samples: int | None = None, lens: bool = True, footprint: bool = True,
+               shutter: bool = True) -> "Guide":
+        """The centre ray of every pixel into the guide's planes; with samples=S the average of S rays per pixel
+        spread over the lens, the pixel's footprint and the shutter (rt_aov_render), which also keeps coverage()."""
+        if samples is None:
+            self._check(lib().rt_guide_render(self._h, width, height), "rt_guide_render")
+        else:
+            p = aov_params(samples=samples, lens=lens, footprint=footprint, shutter=shutter)
+            self._check(lib().rt_aov_render(self._h, width, height, ctypes.byref(p)), "rt_aov_render")
         self.width, self.height = width, height
         return self
+
+    def coverage(self, png_order: bool = True) -> np.ndarray:
+        """(H, W) float32: the share of a pixel's samples that hit something, of the last render(samples=S)."""
+        out = np.zeros((self.height, self.width), np.float32)
+        self._check(lib().rt_aov_coverage(self._h, out.ctypes.data, 1 if png_order else 0), "rt_aov_coverage")
+        return out
 
     def planes(self, png_order: bool = False) -> dict:
         """{"normal", "albedo": (H, W, 3) float32, "depth": (H, W) float32, "prim": (H, W) int32} of the last
@@ -1139,6 +1194,10 @@ class Guide:
         """Device time of the last cast() / render() kernel."""
         return float(lib().rt_guide_last_ms(self._h))
 
+    def last_aov_ms(self) -> float:
+        """Device time of the last render(samples=S) kernel."""
+        return float(lib().rt_aov_last_ms(self._h))
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().rt_guide_destroy(self._h)
@@ -1161,10 +1220,21 @@ def cast_host(scene, rays) -> np.ndarray:
     return out
 
 
-def guide_host(scene, width: int, height: int) -> dict:
-    """Guide.render(width, height).planes() on the host (rt_guide_render_host: no GPU)."""
+def guide_host(scene, width: int, height: int, samples: int | None = None, lens: bool = True, footprint: bool = True,
+               shutter: bool = True) -> dict:
+    """Guide.render(width, height).planes() on the host (rt_guide_render_host: no GPU); with samples=S
+    Guide.render(width, height, S, ...)'s (rt_aov_render_host), and "coverage" (H, W) float32 beside them."""
     d = {"normal": np.zeros((height, width, 3), np.float32), "albedo": np.zeros((height, width, 3), np.float32),
          "depth": np.zeros((height, width), np.float32), "prim": np.zeros((height, width), np.int32)}
+    if samples is not None:
+        d["coverage"] = np.zeros((height, width), np.float32)
+        p = aov_params(samples=samples, lens=lens, footprint=footprint, shutter=shutter)
+        rc = lib().rt_aov_render_host(ctypes.byref(_soa_of(scene)), width, height, ctypes.byref(p), d["normal"].ctypes.data,
+                                      d["albedo"].ctypes.data, d["depth"].ctypes.data, d["prim"].ctypes.data,
+                                      d["coverage"].ctypes.data)
+        if rc != 0:
+            raise RtError(f"rt_aov_render_host failed ({rc})", rc)
+        return d
     rc = lib().rt_guide_render_host(ctypes.byref(_soa_of(scene)), width, height, d["normal"].ctypes.data, d["albedo"].ctypes.data,
                                     d["depth"].ctypes.data, d["prim"].ctypes.data)
     if rc != 0:
@@ -1226,14 +1296,15 @@ def read_adaptive_checkpoint(path: str, threshold: float | None = None) -> tuple
 
 def _final_denoise(target, denoise, curr_scene: Scene, settings: render_settings, device: int):
     """target.denoise(denoise).  A dict with guide=True (and, if wanted, guide_params=...) beside the denoiser's
-    fields takes the guided filter: a Guide of the scene on the draw's device, rendered at the image's size."""
-    if isinstance(denoise, dict) and ("guide" in denoise or "guide_params" in denoise):
+    fields takes the guided filter: a Guide of the scene on the draw's device, rendered at the image's size; with
+    guide_samples=S its planes are the averages of S rays per pixel (Guide.render(..., samples=S))."""
+    if isinstance(denoise, dict) and ("guide" in denoise or "guide_params" in denoise or "guide_samples" in denoise):
         fields = dict(denoise)
-        use, gains = fields.pop("guide", False), fields.pop("guide_params", None)
+        use, gains, samples = fields.pop("guide", False), fields.pop("guide_params", None), fields.pop("guide_samples", None)
         if use:
             g = Guide(curr_scene, device)
             try:
-                g.render(settings.image_width, settings.image_height)
+                g.render(settings.image_width, settings.image_height, samples)
                 return target.denoise(fields, guide=g, guide_params=gains)
             finally:
                 g.close()
@@ -1264,7 +1335,8 @@ def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context 
     statistics are never silently restarted from a later frame buffer.
 
     denoise=True (the shipped parameters) or parameters as denoise_params() takes them (a dict may also hold
-    guide=True for the feature-guided filter, and guide_params): a noise monitor is
+    guide=True for the feature-guided filter, guide_params, and guide_samples=S for planes averaged over S rays
+    per pixel): a noise monitor is
     attached if until_noise has not attached one (it never stops the draw then), and the image returned is
     NoiseMonitor.denoise() of the final state instead of the plain one (needs two frame buffers); on_image
     still gets the plain images.  None leaves the function exactly as it is without it."""
@@ -1356,7 +1428,8 @@ def draw_adaptive(curr_scene: Scene, settings: render_settings, ctx: Context | N
     tighter threshold.
 
     denoise=True (the shipped parameters) or parameters as denoise_params() takes them (a dict may also hold
-    guide=True for the feature-guided filter, and guide_params): the image returned is
+    guide=True for the feature-guided filter, guide_params, and guide_samples=S for planes averaged over S rays
+    per pixel): the image returned is
     AdaptiveAccumulator.denoise() of the final state, every pixel at its own tile's count, instead of the plain
     one (every tile needs two frame buffers); on_image still gets the plain images."""
     if settings.image_height <= 0:

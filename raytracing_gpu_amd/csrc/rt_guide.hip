@@ -1,6 +1,6 @@
 // rt_guide.hip -- the device half of the guide (include/rt_hip.h, "ray casts and feature buffers"): a validated
 // copy of the scene in device memory, the cast kernel (one lane per ray), the centre-ray pass into the feature
-// planes and their 8-bit pictures.  The first hit is rt_first_hit.h's, which the host twin (rt_guide_host.cpp)
+// planes, the pass that averages them over a sample pattern (rt_aov.h) and their 8-bit pictures.  The first hit is rt_first_hit.h's, which the host twin (rt_guide_host.cpp)
 // compiles too.  Nothing here touches a context or the render kernels; rt_progressive.hip reads the planes
 // through rt_guide.h for the guided denoise.
 //
@@ -15,6 +15,7 @@
 
 #include "../../include/rt_hip.h"
 #include "rt_accum_blob.h"
+#include "rt_aov.h"
 #include "rt_devbuf.h"
 #include "rt_first_hit.h"
 #include "rt_guide.h"
@@ -52,6 +53,27 @@ __global__ __launch_bounds__(256) void guide_render_kernel(const rt_scene_soa sc
   prim[p] = h.prim;
 }
 
+// The same lanes, each looping over the pattern's samples (rtaov::pixel).  Every lane of a wave is on the same
+// sample at the same time: the table is read through the loop counter alone (scalar loads), and the lens offset
+// and the time are wave-uniform, so a wave's rays stay as coherent as the centre pass's.
+// Four waves per SIMD, the centre pass's occupancy: the sums and the loop take the kernel from 127 to 152 VGPRs
+// (three waves) left alone; held to 128 it spills 80 bytes of scratch and is the faster one.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void aov_render_kernel(
+    const rt_scene_soa sc, int width, int height, int samples, int lens, const float* __restrict__ table,
+    float* __restrict__ normal, float* __restrict__ albedo, float* __restrict__ depth, int32_t* __restrict__ prim,
+    float* __restrict__ coverage) {
+  const int i = blockIdx.x * 16 + (threadIdx.x & 15), j = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (i >= width || j >= height) return;
+  rtaov::Pixel px;
+  rtaov::pixel(sc, table, samples, lens, i, j, width, height, px);
+  const long long p = (long long)j * width + i;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) normal[3 * p + c] = px.n[c], albedo[3 * p + c] = px.albedo[c];
+  depth[p] = px.depth;
+  prim[p] = px.prim;
+  coverage[p] = px.coverage;
+}
+
 __global__ __launch_bounds__(kBlock) void guide_image_kernel(const float* __restrict__ plane, int normal, long long n_values,
                                                             uint8_t* __restrict__ out) {
   const long long k = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -85,10 +107,14 @@ struct RT_INTERNAL rt_guide {
   int32_t width = 0, height = 0;  // of the planes; 0 before the first render
   DevBuf<float> normal, albedo, depth;
   DevBuf<int32_t> prim;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool timed = false;
+  DevBuf<float> coverage, table;  // rt_aov_render's: hits / samples per pixel, the pattern
+  bool averaged = false;          // the planes came from rt_aov_render
+  hipEvent_t ev[2] = {nullptr, nullptr}, aov_ev[2] = {nullptr, nullptr};
+  bool timed = false, aov_timed = false;
   ~rt_guide() {
     for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : aov_ev)
       if (e) (void)hipEventDestroy(e);
   }
 };
@@ -164,7 +190,9 @@ int rt_guide_create(const rt_scene_soa* scene, int hip_device, rt_guide** out) {
       (rc = upload(scene->images, (size_t)scene->n_images, g->images, &g->dev.images)) ||
       (rc = upload(scene->texels, (size_t)scene->n_texels, g->texels, &g->dev.texels)))
     return rc;
-  if (hipEventCreate(&g->ev[0]) != hipSuccess || hipEventCreate(&g->ev[1]) != hipSuccess) return RT_ERR_HIP;
+  if (hipEventCreate(&g->ev[0]) != hipSuccess || hipEventCreate(&g->ev[1]) != hipSuccess ||
+      hipEventCreate(&g->aov_ev[0]) != hipSuccess || hipEventCreate(&g->aov_ev[1]) != hipSuccess)
+    return RT_ERR_HIP;
   *out = g.release();
   return RT_OK;
 }
@@ -200,6 +228,7 @@ int rt_guide_render(rt_guide* g, int32_t width, int32_t height) {
   if (hipSetDevice(g->device) != hipSuccess) return RT_ERR_HIP;
   const size_t px = (size_t)width * (size_t)height;
   g->width = g->height = 0;
+  g->averaged = false;
   if (g->normal.reserve(3 * px) == DevBuf<float>::failed || g->albedo.reserve(3 * px) == DevBuf<float>::failed ||
       g->depth.reserve(px) == DevBuf<float>::failed || g->prim.reserve(px) == DevBuf<int32_t>::failed)
     return RT_ERR_NOMEM;
@@ -247,6 +276,52 @@ int rt_guide_image(rt_guide* g, int32_t which, uint8_t* out, int32_t png_order) 
   if (hipMemcpy(tmp.get(), img.dev(), n, hipMemcpyDeviceToHost) != hipSuccess) return RT_ERR_HIP;
   flip_rows(out, tmp.get(), (size_t)g->height, (size_t)g->width * 3);
   return RT_OK;
+}
+
+int rt_aov_render(rt_guide* g, int32_t width, int32_t height, const rt_aov_params* params) {
+  if (!g || width < 1 || height < 1 || (long long)width * height > (1LL << 30) || (height + 15) / 16 > 65535) return RT_ERR_ARG;
+  rt_aov_params p;
+  if (params) p = *params;
+  else rt_aov_params_default(&p);
+  if (!rtaov::valid(p)) return RT_ERR_ARG;
+  if (hipSetDevice(g->device) != hipSuccess) return RT_ERR_HIP;
+  const size_t px = (size_t)width * (size_t)height;
+  g->width = g->height = 0;
+  g->averaged = false;
+  if (g->normal.reserve(3 * px) == DevBuf<float>::failed || g->albedo.reserve(3 * px) == DevBuf<float>::failed ||
+      g->depth.reserve(px) == DevBuf<float>::failed || g->prim.reserve(px) == DevBuf<int32_t>::failed ||
+      g->coverage.reserve(px) == DevBuf<float>::failed ||
+      g->table.reserve((size_t)rtaov::kMaxSamples * rtaov::kEntry) == DevBuf<float>::failed)
+    return RT_ERR_NOMEM;
+  float table[rtaov::kMaxSamples * rtaov::kEntry];
+  rtaov::pattern(p, table);
+  if (hipMemcpy(g->table.get(), table, (size_t)p.samples * rtaov::kEntry * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    return RT_ERR_HIP;
+  if (hipEventRecord(g->aov_ev[0], nullptr) != hipSuccess) return RT_ERR_HIP;
+  hipLaunchKernelGGL(aov_render_kernel, dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)), dim3(256), 0, nullptr,
+                     g->dev, width, height, p.samples, p.lens, g->table.get(), g->normal.get(), g->albedo.get(), g->depth.get(),
+                     g->prim.get(), g->coverage.get());
+  if (hipGetLastError() != hipSuccess || hipEventRecord(g->aov_ev[1], nullptr) != hipSuccess ||
+      hipStreamSynchronize(nullptr) != hipSuccess)
+    return RT_ERR_HIP;
+  g->aov_timed = true;
+  g->width = width, g->height = height;
+  g->averaged = true;
+  return RT_OK;
+}
+
+int rt_aov_coverage(rt_guide* g, float* out, int32_t png_order) {
+  if (!g || (png_order != 0 && png_order != 1)) return RT_ERR_ARG;
+  if (!g->width || !g->averaged) return RT_ERR_STATE;
+  if (hipSetDevice(g->device) != hipSuccess) return RT_ERR_HIP;
+  if (png_order && out && rtctx::device_ptr(out)) return RT_ERR_ARG;
+  return plane_out(g, g->coverage.get(), 1, out, png_order);
+}
+
+float rt_aov_last_ms(const rt_guide* g) {
+  float ms = 0.0f;
+  if (!g || !g->aov_timed || hipEventElapsedTime(&ms, g->aov_ev[0], g->aov_ev[1]) != hipSuccess) return 0.0f;
+  return ms;
 }
 
 float rt_guide_last_ms(const rt_guide* g) {

@@ -1,10 +1,11 @@
-// rt_guide_host.cpp -- the host-only twin of the guide (rt_guide_cast_host, rt_guide_render_host and the
-// rt_guide_denoise_*_blob calls of include/rt_hip.h): ray casts, feature planes and the guided denoise of a
-// checkpoint without a context or a GPU.  Plain C++ with no HIP include; a stand-alone program links this file
+// rt_guide_host.cpp -- the host-only twin of the guide (rt_guide_cast_host, rt_guide_render_host, the
+// rt_guide_denoise_*_blob calls and the host-only rt_aov_* calls of include/rt_hip.h): ray casts, feature planes,
+// planes averaged over a sample pattern and the guided denoise of a checkpoint without a context or a GPU.  Plain C++ with no HIP include; a stand-alone program links this file
 // with rt_validate.cpp and the rt_*_blob.cpp files.
 //
 // The first hit is rt_first_hit.h's, which the device kernels (rt_guide.hip) compile too, and the guided weight
 // is rt_denoise_math.h's through the twin of rt_denoise_blob.cpp, so each pair agrees bit for bit.
+#include "rt_aov.h"
 #include "rt_denoise_math.h"
 #include "rt_first_hit.h"
 
@@ -67,6 +68,47 @@ int rt_guide_render_host(const rt_scene_soa* scene, int32_t width, int32_t heigh
       }
       if (depth) depth[p] = h.t;
       if (prim) prim[p] = h.prim;
+    }
+  return RT_OK;
+}
+
+void rt_aov_params_default(rt_aov_params* p) {
+  if (!p) return;
+  p->samples = 16;
+  p->lens = p->footprint = p->shutter = 1;
+}
+
+int rt_aov_pattern(const rt_aov_params* params, float* out) {
+  rt_aov_params p;
+  if (params) p = *params;
+  else rt_aov_params_default(&p);
+  if (!out || !rtaov::valid(p)) return RT_ERR_ARG;
+  rtaov::pattern(p, out);
+  return RT_OK;
+}
+
+int rt_aov_render_host(const rt_scene_soa* scene, int32_t width, int32_t height, const rt_aov_params* params, float* normal,
+                       float* albedo, float* depth, int32_t* prim, float* coverage) {
+  rt_aov_params p;
+  if (params) p = *params;
+  else rt_aov_params_default(&p);
+  if (width < 1 || height < 1 || !rtaov::valid(p)) return RT_ERR_ARG;
+  const int rc = scene_check(scene);
+  if (rc) return rc;
+  float table[rtaov::kMaxSamples * rtaov::kEntry];
+  rtaov::pattern(p, table);
+  for (int32_t j = 0; j < height; ++j)
+    for (int32_t i = 0; i < width; ++i) {
+      rtaov::Pixel px;
+      rtaov::pixel(*scene, table, p.samples, p.lens, i, j, width, height, px);
+      const size_t k = (size_t)j * (size_t)width + (size_t)i;
+      for (int c = 0; c < 3; ++c) {
+        if (normal) normal[3 * k + c] = px.n[c];
+        if (albedo) albedo[3 * k + c] = px.albedo[c];
+      }
+      if (depth) depth[k] = px.depth;
+      if (prim) prim[k] = px.prim;
+      if (coverage) coverage[k] = px.coverage;
     }
   return RT_OK;
 }
