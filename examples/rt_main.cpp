@@ -47,6 +47,9 @@
 //     --guide-samples S     with --guided or --aov: the planes are averages of S rays per pixel spread over the
 //                           pixel, the lens and the shutter (rt_aov_render with the other defaults); --aov then
 //                           also writes PREFIX_coverage.ppm, the share of a pixel's rays that hit, in grey
+//     --guide-specular N    with --guided or --aov: the planes follow mirrors and glass through at most N
+//                           continuation rays (rt_spec_render with the other defaults; 0..16), from the centre
+//                           ray or, with --guide-samples, from each of the S rays
 //
 // Writes OUT.ppm (binary P6, top row first) and one JSON line per draw on stdout.  Files written
 // more than once go to a temporary name first and are renamed into place.
@@ -321,7 +324,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: rt_main SCENE WIDTH SPP_PER_FB NO_FB OUT.ppm [--devices 0,1] [--gather rccl|host] "
                     "[--band-rows B] [--repeat K] [--depth D] [--height H] [--obj PATH] [--tex PATH] [--progressive K] [--checkpoint FILE] "
                     "[--until-noise T [--noisy-fraction F]] [--adaptive K --until-noise T [--max-above M] [--min-fbs F] "
-                    "[--adaptive-checkpoint FILE] [--dilate R] [--reopen]] [--denoise OUT2.ppm [--guided]] [--aov PREFIX] [--guide-samples S]\n");
+                    "[--adaptive-checkpoint FILE] [--dilate R] [--reopen]] [--denoise OUT2.ppm [--guided]] [--aov PREFIX] [--guide-samples S] [--guide-specular N]\n");
     return 2;
   }
   const char* name = argv[1];
@@ -335,6 +338,8 @@ int main(int argc, char** argv) {
   const char *obj_path = nullptr, *tex_path = nullptr, *ckpt_path = nullptr, *adaptive_ckpt = nullptr, *denoised = nullptr, *aov = nullptr;
   bool guided = false, have_guide_samples = false;
   int guide_samples = 0;
+  bool have_guide_specular = false;
+  int guide_specular = 0;
   int dilate = 0;
   bool reopen = false, have_resume_opts = false;
   int height = 0;
@@ -367,6 +372,7 @@ int main(int argc, char** argv) {
     else if (a == "--guided") guided = true;
     else if (a == "--aov") aov = v, ++k;
     else if (a == "--guide-samples") have_guide_samples = true, guide_samples = atoi(v), ++k;
+    else if (a == "--guide-specular") have_guide_specular = true, guide_specular = atoi(v), ++k;
     else if (a == "--noisy-fraction") have_fraction = true, noisy_fraction = atof(v), ++k;
     else return die("unknown option", argv[k]);
   }
@@ -389,6 +395,8 @@ int main(int argc, char** argv) {
   if (guided && !denoised) return die("--guided", "needs --denoise OUT2.ppm");
   if (have_guide_samples && !guided && !aov) return die("--guide-samples", "needs --guided or --aov PREFIX");
   if (have_guide_samples && (guide_samples < 1 || guide_samples > 256)) return die("--guide-samples", "S must be 1..256");
+  if (have_guide_specular && !guided && !aov) return die("--guide-specular", "needs --guided or --aov PREFIX");
+  if (have_guide_specular && (guide_specular < 0 || guide_specular > 16)) return die("--guide-specular", "N must be 0..16");
   if ((guided || aov) && !devices.empty()) return die("--guided / --aov", "one GPU only (no --devices)");
   if (denoised && s.no_fb > 32768) return die("--denoise", "a noise monitor accepts at most 32768 frame buffers");
   if (until_noise && s.no_fb > 32768) return die("--until-noise", "a noise monitor accepts at most 32768 frame buffers");
@@ -453,10 +461,15 @@ int main(int argc, char** argv) {
   rt_guide* guide = nullptr;
   if (guided || aov) {  // the feature planes of the camera's centre rays, from the guide's own copy of the scene
     if (rt_guide_create(soa, 0, &guide)) return die("rt_guide_create", name);
-    if (have_guide_samples) {  // ... or of S rays per pixel, averaged
-      rt_aov_params ap;
-      rt_aov_params_default(&ap);
-      ap.samples = guide_samples;
+    rt_aov_params ap;
+    rt_aov_params_default(&ap);
+    ap.samples = guide_samples;
+    if (have_guide_specular) {  // ... of what mirrors and glass show, from the centre ray or from S rays
+      rt_spec_params sp;
+      rt_spec_params_default(&sp);
+      sp.max_bounces = guide_specular;
+      if (rt_spec_render(guide, a.width, a.height, have_guide_samples ? &ap : nullptr, &sp)) return die("rt_spec_render", name);
+    } else if (have_guide_samples) {  // ... or of S rays per pixel, averaged
       if (rt_aov_render(guide, a.width, a.height, &ap)) return die("rt_aov_render", name);
     } else if (rt_guide_render(guide, a.width, a.height)) {
       return die("rt_guide_render", name);
@@ -478,7 +491,13 @@ int main(int argc, char** argv) {
         png[3 * p] = png[3 * p + 1] = png[3 * p + 2] = (uint8_t)(int)(256.0f * (r > 0.999f ? 0.999f : r));
       }
       if (!write_file(path, head, png.data(), png.size())) return die("write", path.c_str());
-      printf("{\"aov\": \"%s\", \"guide_ms\": %.3f, \"guide_samples\": %d}\n", aov, rt_aov_last_ms(guide), guide_samples);
+      if (have_guide_specular)
+        printf("{\"aov\": \"%s\", \"guide_ms\": %.3f, \"guide_samples\": %d, \"guide_specular\": %d}\n", aov, rt_spec_last_ms(guide),
+               guide_samples, guide_specular);
+      else
+        printf("{\"aov\": \"%s\", \"guide_ms\": %.3f, \"guide_samples\": %d}\n", aov, rt_aov_last_ms(guide), guide_samples);
+    } else if (aov && have_guide_specular) {
+      printf("{\"aov\": \"%s\", \"guide_ms\": %.3f, \"guide_specular\": %d}\n", aov, rt_spec_last_ms(guide), guide_specular);
     } else if (aov) {
       printf("{\"aov\": \"%s\", \"guide_ms\": %.3f}\n", aov, rt_guide_last_ms(guide));
     }

@@ -862,6 +862,85 @@ int rt_aov_render_host(const rt_scene_soa* scene, int32_t width, int32_t height,
 /* Device time in ms of the last averaged pass's kernel; 0 before one. */
 float rt_aov_last_ms(const rt_guide* g);
 
+/* ------------------------------------------------------------------ casts and planes through specular surfaces */
+/* The casts and planes above describe the first surface a ray meets.  On a mirror or a glass ball that surface
+ * says nothing about the picture, which is of whatever the mirror shows.  A chain follows a ray through such
+ * surfaces without a random number: a metal of little fuzz reflects, a dielectric refracts unless it cannot, and
+ * the answer is the first surface that is neither, with the tint gathered on the way and the length travelled.
+ * It serves "what do I see along this ray, through the mirror" and feature planes that have edges where the
+ * reflected or refracted picture has them.  (A family of its own because the guide's and the averaged planes' are
+ * closed.)  Nothing above changes what it returns.
+ *
+ * Everything is in float, one correctly rounded operation per operator, left to right, unless it says double;
+ * a segment is one cast of the guide, of which only p, n, front, material, albedo, t and prim are read.  dot is
+ * (x x + y y) + z z, v / s is (1.0f / s) v as in vec3.h.  The chain of a ray e0 = (o, d, time):
+ *
+ *   1. h = cast(e0), thr = (1, 1, 1), k = 0.
+ *   2. h.prim < 0: the chain ends, RT_SPEC_MISS when k = 0, otherwise RT_SPEC_ESCAPED.
+ *   3. m = materials[h.material] is specular when it is an RT_MAT_METAL with m.param <= max_fuzz, or an
+ *      RT_MAT_DIELECTRIC and glass is set.  Anything else ends the chain: RT_SPEC_SURFACE.  (A medium is its
+ *      boundary with the phase material, as cast says, and therefore ends it.)
+ *   4. k == max_bounces: RT_SPEC_LIMIT.
+ *   5. ud = d / sqrtf(dot(d, d)).
+ *   6. Metal (material.h:46-54 with the fuzz term at its mean, 0):  dir = ud - (2.0f dot(ud, n)) n;
+ *      !(dot(dir, n) > 0): RT_SPEC_ABSORBED, the reference's scatter returning false;  otherwise
+ *      thr = thr * h.albedo per component.
+ *   7. Dielectric (material.h:67-90 without Schlick's random choice: the refraction whenever there is one):
+ *        ratio = front ? 1.0f / ir : ir;   c = fminf(dot(-ud, n), 1.0f);   s = sqrtf(1.0f - c c)
+ *        ratio s > 1.0f:  dir as the metal's
+ *        otherwise (vec3.h:152-158):  perp = ratio (ud + c n)
+ *                                     par  = -sqrtf(fabsf((float)(1.0 - (double)dot(perp, perp))))
+ *                                     dir  = perp + par n
+ *   8. The next ray is (h.p, dir, time): k = k + 1, h = cast of it, back to 2.
+ *
+ * Per ray the chain gives the last cast's rt_guide_hit unchanged (for RT_SPEC_ESCAPED the hit before the miss; its
+ * albedo stays that surface's own texture value) and an rt_spec_path.  depth is in the primary ray's parameter
+ * units, so that neighbouring pixels compare whatever the length of the camera's direction:
+ *
+ *   depth = t_0                                                            no continuation segment hit
+ *   depth = t_0 + (sum of t_k sqrtf(dot(d_k, d_k)), k >= 1) / sqrtf(dot(d_0, d_0))
+ *
+ * over the continuation segments that hit; the sum starts as its first term and takes the others in order.  With
+ * max_bounces = 0 the hit is cast's, byte for byte.  The chain is stated once, in csrc/rt_spec.h, for both halves. */
+enum rt_spec_status { RT_SPEC_MISS = 0, RT_SPEC_SURFACE = 1, RT_SPEC_ESCAPED = 2, RT_SPEC_LIMIT = 3, RT_SPEC_ABSORBED = 4 };
+typedef struct rt_spec_params {
+  int32_t max_bounces;  /* 0..16 continuation segments */
+  float max_fuzz;       /* 0..1: a metal of at most this fuzz is a mirror */
+  int32_t glass;        /* 0 or 1: follow dielectrics */
+  int32_t reserved;     /* 0 */
+} rt_spec_params;       /* 16 bytes */
+typedef struct rt_spec_path {
+  int32_t bounces;         /* continuation segments cast */
+  int32_t status;          /* rt_spec_status */
+  int32_t first_prim;      /* the primary hit's prim and material; -1 for a miss */
+  int32_t first_material;
+  float throughput[3];     /* thr */
+  float depth;             /* 0 for a miss */
+} rt_spec_path;            /* 32 bytes */
+/* max_bounces 4, max_fuzz 0.1, glass 1 (DESIGN.md 3.10 has the measurements behind max_fuzz). */
+void rt_spec_params_default(rt_spec_params* p);
+/* The chains of n rays in rt_guide_cast's layout.  rays, hits and paths are each a device or a host pointer; hits
+ * or paths may be NULL.  p = NULL takes the defaults; RT_ERR_ARG for a field outside its range (so everywhere
+ * below).  n = 0 is RT_OK. */
+int rt_spec_cast(rt_guide* g, const float* rays, long long n, const rt_spec_params* p, rt_guide_hit* hits, rt_spec_path* paths);
+/* The averaged pass with a chain per sample, into the guide's planes and coverage, so the planes, image, coverage
+ * and guided-denoise calls work on them as they are.  aov = NULL means the centre ray: samples 1, lens 0,
+ * footprint 0, shutter 0 (not the averaged pass's defaults); spec = NULL takes the defaults.  Per sample the normal
+ * is the chain's hit's n (0 for RT_SPEC_MISS), the albedo is thr * albedo per component with the background in
+ * place of the surface for RT_SPEC_MISS and RT_SPEC_ESCAPED, and the depth is the path's.  Whether a sample counts
+ * as a hit, and so coverage, prim and which samples' depths are averaged, is decided by the primary ray: the
+ * silhouette stays the first surface's.  Sums, order and divisions are the averaged pass's.  With max_bounces = 0
+ * the five planes are rt_aov_render's byte for byte; with aov = NULL as well, rt_guide_render's. */
+int rt_spec_render(rt_guide* g, int32_t width, int32_t height, const rt_aov_params* aov, const rt_spec_params* spec);
+/* Host only (no GPU; csrc/rt_guide_host.cpp): the same answers from the same code.  Host pointers, each output
+ * may be NULL, row 0 the bottom row. */
+int rt_spec_cast_host(const rt_scene_soa* scene, const float* rays, long long n, const rt_spec_params* p, rt_guide_hit* hits,
+                      rt_spec_path* paths);
+int rt_spec_render_host(const rt_scene_soa* scene, int32_t width, int32_t height, const rt_aov_params* aov,
+                        const rt_spec_params* spec, float* normal, float* albedo, float* depth, int32_t* prim, float* coverage);
+/* Device time in ms of the last rt_spec_cast or rt_spec_render kernel; 0 before one. */
+float rt_spec_last_ms(const rt_guide* g);
+
 /* ------------------------------------------------------------------ host scene library */
 /* Builds one of the reference scenes (scenes.h) on the host: "basic", "first", "big1" (alias
  * "random"), "two_spheres", "two_perlin", "cornell", "cornell_smoke", "triangle", "triangles",

@@ -209,6 +209,25 @@ class rt_aov_params(ctypes.Structure):
         return {"samples": int(self.samples), "lens": int(self.lens), "footprint": int(self.footprint), "shutter": int(self.shutter)}
 
 
+class rt_spec_params(ctypes.Structure):
+    """include/rt_hip.h rt_spec_params (16 bytes)."""
+    _fields_ = [("max_bounces", c_int32), ("max_fuzz", c_float), ("glass", c_int32), ("reserved", c_int32)]
+
+    def as_dict(self) -> dict:
+        return {"max_bounces": int(self.max_bounces), "max_fuzz": float(self.max_fuzz), "glass": int(self.glass)}
+
+
+class rt_spec_path(ctypes.Structure):
+    """include/rt_hip.h rt_spec_path (32 bytes)."""
+    _fields_ = [("bounces", c_int32), ("status", c_int32), ("first_prim", c_int32), ("first_material", c_int32),
+                ("throughput", c_float * 3), ("depth", c_float)]
+
+
+SPEC_PATH_DTYPE = np.dtype([("bounces", "<i4"), ("status", "<i4"), ("first_prim", "<i4"), ("first_material", "<i4"),
+                            ("throughput", "<f4", 3), ("depth", "<f4")])
+SPEC_MISS, SPEC_SURFACE, SPEC_ESCAPED, SPEC_LIMIT, SPEC_ABSORBED = range(5)  # rt_spec_status
+
+
 # Every entry point of include/rt_hip.h: name -> (restype, argtypes)
 ABI = {
     "rt_ctx_create": (c_int, [c_int, POINTER(c_void_p)]),
@@ -308,6 +327,13 @@ ABI = {
     "rt_aov_render_host": (c_int, [POINTER(rt_scene_soa), c_int32, c_int32, POINTER(rt_aov_params), c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),
     "rt_aov_last_ms": (c_float, [c_void_p]),
+    "rt_spec_params_default": (None, [POINTER(rt_spec_params)]),
+    "rt_spec_cast": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, POINTER(rt_spec_params), c_void_p, c_void_p]),
+    "rt_spec_render": (c_int, [c_void_p, c_int32, c_int32, POINTER(rt_aov_params), POINTER(rt_spec_params)]),
+    "rt_spec_cast_host": (c_int, [POINTER(rt_scene_soa), c_void_p, ctypes.c_longlong, POINTER(rt_spec_params), c_void_p, c_void_p]),
+    "rt_spec_render_host": (c_int, [POINTER(rt_scene_soa), c_int32, c_int32, POINTER(rt_aov_params), POINTER(rt_spec_params),
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rt_spec_last_ms": (c_float, [c_void_p]),
     "rt_scene_build": (c_int, [c_char_p, POINTER(c_void_p)]),
     "rt_scene_build_ex": (c_int, [c_char_p, c_void_p, POINTER(c_void_p)]),
     "rt_obj_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
@@ -408,6 +434,31 @@ def aov_params(params=None, **kw) -> rt_aov_params:
             raise TypeError(f"rt_aov_params has no field {k!r}")
         setattr(p, k, int(v))
     return p
+
+
+def spec_params(params=None, **kw) -> rt_spec_params:
+    """How casts and planes follow mirrors and glass (include/rt_hip.h): the shipped defaults, or a copy of params
+    (an rt_spec_params, a dict of its fields, an int for max_bounces, True or None for the defaults), with the
+    fields of kw set."""
+    p = rt_spec_params()
+    if isinstance(params, rt_spec_params):
+        ctypes.memmove(ctypes.byref(p), ctypes.byref(params), ctypes.sizeof(p))
+    else:
+        lib().rt_spec_params_default(ctypes.byref(p))
+        if isinstance(params, dict):
+            kw = {**params, **kw}
+        elif params is not None and not isinstance(params, bool):
+            kw = {"max_bounces": params, **kw}
+    for k, v in kw.items():
+        if k not in ("max_bounces", "max_fuzz", "glass"):
+            raise TypeError(f"rt_spec_params has no field {k!r}")
+        setattr(p, k, float(v) if k == "max_fuzz" else int(v))
+    return p
+
+
+def _centre_or(samples, lens, footprint, shutter):
+    """The rt_aov_params pointer of a specular render: NULL (the centre ray) without samples."""
+    return None if samples is None else ctypes.byref(aov_params(samples=samples, lens=lens, footprint=footprint, shutter=shutter))
 
 
 def aov_pattern(params=None, **kw) -> np.ndarray:
@@ -1153,11 +1204,27 @@ class Guide:
         """cast() between caller memory (device or host addresses)."""
         self._check(lib().rt_guide_cast(self._h, c_void_p(rays_ptr), n, c_void_p(out_ptr)), "rt_guide_cast")
 
+    def trace(self, rays, **spec) -> tuple[np.ndarray, np.ndarray]:
+        """cast() through mirrors and glass (rt_spec_cast): (hits, paths), the last surface of every ray's chain as
+        GUIDE_HIT_DTYPE and the chain as SPEC_PATH_DTYPE: bounces, status (SPEC_*), first_prim, first_material,
+        throughput, depth.  spec: the fields of spec_params()."""
+        r, p = _rays(rays), spec_params(**spec)
+        hits, paths = np.zeros(len(r), GUIDE_HIT_DTYPE), np.zeros(len(r), SPEC_PATH_DTYPE)
+        self._check(lib().rt_spec_cast(self._h, r.ctypes.data, len(r), ctypes.byref(p), hits.ctypes.data, paths.ctypes.data),
+                    "rt_spec_cast")
+        return hits, paths
+
     def render(self, width: int, height: int, samples: int | None = None, lens: bool = True, footprint: bool = True,
-               shutter: bool = True) -> "Guide":
+               shutter: bool = True, specular=None) -> "Guide":
         """The centre ray of every pixel into the guide's planes; with samples=S the average of S rays per pixel
-        spread over the lens, the pixel's footprint and the shutter (rt_aov_render), which also keeps coverage()."""
-        if samples is None:
+        spread over the lens, the pixel's footprint and the shutter (rt_aov_render), which also keeps coverage().
+        specular=True, a bounce limit or what spec_params() takes: the planes of what mirrors and glass show
+        (rt_spec_render; coverage() is kept); None or False changes nothing."""
+        if specular is not None and specular is not False:
+            sp = spec_params(specular)
+            self._check(lib().rt_spec_render(self._h, width, height, _centre_or(samples, lens, footprint, shutter), ctypes.byref(sp)),
+                        "rt_spec_render")
+        elif samples is None:
             self._check(lib().rt_guide_render(self._h, width, height), "rt_guide_render")
         else:
             p = aov_params(samples=samples, lens=lens, footprint=footprint, shutter=shutter)
@@ -1194,6 +1261,10 @@ class Guide:
         """Device time of the last cast() / render() kernel."""
         return float(lib().rt_guide_last_ms(self._h))
 
+    def last_spec_ms(self) -> float:
+        """Device time of the last trace() / render(specular=...) kernel."""
+        return float(lib().rt_spec_last_ms(self._h))
+
     def last_aov_ms(self) -> float:
         """Device time of the last render(samples=S) kernel."""
         return float(lib().rt_aov_last_ms(self._h))
@@ -1220,12 +1291,33 @@ def cast_host(scene, rays) -> np.ndarray:
     return out
 
 
+def trace_host(scene, rays, **spec) -> tuple[np.ndarray, np.ndarray]:
+    """Guide.trace() on the host (rt_spec_cast_host: no GPU), bit-identical to the device's."""
+    r, p = _rays(rays), spec_params(**spec)
+    hits, paths = np.zeros(len(r), GUIDE_HIT_DTYPE), np.zeros(len(r), SPEC_PATH_DTYPE)
+    rc = lib().rt_spec_cast_host(ctypes.byref(_soa_of(scene)), r.ctypes.data, len(r), ctypes.byref(p), hits.ctypes.data,
+                                 paths.ctypes.data)
+    if rc != 0:
+        raise RtError(f"rt_spec_cast_host failed ({rc})", rc)
+    return hits, paths
+
+
 def guide_host(scene, width: int, height: int, samples: int | None = None, lens: bool = True, footprint: bool = True,
-               shutter: bool = True) -> dict:
+               shutter: bool = True, specular=None) -> dict:
     """Guide.render(width, height).planes() on the host (rt_guide_render_host: no GPU); with samples=S
-    Guide.render(width, height, S, ...)'s (rt_aov_render_host), and "coverage" (H, W) float32 beside them."""
+    Guide.render(width, height, S, ...)'s (rt_aov_render_host), and "coverage" (H, W) float32 beside them; with
+    specular=... Guide.render(..., specular=...)'s (rt_spec_render_host), with "coverage" too."""
     d = {"normal": np.zeros((height, width, 3), np.float32), "albedo": np.zeros((height, width, 3), np.float32),
          "depth": np.zeros((height, width), np.float32), "prim": np.zeros((height, width), np.int32)}
+    if specular is not None and specular is not False:
+        d["coverage"] = np.zeros((height, width), np.float32)
+        sp = spec_params(specular)
+        rc = lib().rt_spec_render_host(ctypes.byref(_soa_of(scene)), width, height, _centre_or(samples, lens, footprint, shutter),
+                                       ctypes.byref(sp), d["normal"].ctypes.data, d["albedo"].ctypes.data, d["depth"].ctypes.data,
+                                       d["prim"].ctypes.data, d["coverage"].ctypes.data)
+        if rc != 0:
+            raise RtError(f"rt_spec_render_host failed ({rc})", rc)
+        return d
     if samples is not None:
         d["coverage"] = np.zeros((height, width), np.float32)
         p = aov_params(samples=samples, lens=lens, footprint=footprint, shutter=shutter)
@@ -1297,14 +1389,16 @@ def read_adaptive_checkpoint(path: str, threshold: float | None = None) -> tuple
 def _final_denoise(target, denoise, curr_scene: Scene, settings: render_settings, device: int):
     """target.denoise(denoise).  A dict with guide=True (and, if wanted, guide_params=...) beside the denoiser's
     fields takes the guided filter: a Guide of the scene on the draw's device, rendered at the image's size; with
-    guide_samples=S its planes are the averages of S rays per pixel (Guide.render(..., samples=S))."""
-    if isinstance(denoise, dict) and ("guide" in denoise or "guide_params" in denoise or "guide_samples" in denoise):
+    guide_samples=S its planes are the averages of S rays per pixel (Guide.render(..., samples=S)), with
+    guide_specular=... they follow mirrors and glass (Guide.render(..., specular=...))."""
+    if isinstance(denoise, dict) and any(k in denoise for k in ("guide", "guide_params", "guide_samples", "guide_specular")):
         fields = dict(denoise)
         use, gains, samples = fields.pop("guide", False), fields.pop("guide_params", None), fields.pop("guide_samples", None)
+        specular = fields.pop("guide_specular", None)
         if use:
             g = Guide(curr_scene, device)
             try:
-                g.render(settings.image_width, settings.image_height, samples)
+                g.render(settings.image_width, settings.image_height, samples, specular=specular)
                 return target.denoise(fields, guide=g, guide_params=gains)
             finally:
                 g.close()
@@ -1335,8 +1429,8 @@ def draw_progressive(curr_scene: Scene, settings: render_settings, ctx: Context 
     statistics are never silently restarted from a later frame buffer.
 
     denoise=True (the shipped parameters) or parameters as denoise_params() takes them (a dict may also hold
-    guide=True for the feature-guided filter, guide_params, and guide_samples=S for planes averaged over S rays
-    per pixel): a noise monitor is
+    guide=True for the feature-guided filter, guide_params, guide_samples=S for planes averaged over S rays
+    per pixel and guide_specular=... for planes that follow mirrors and glass): a noise monitor is
     attached if until_noise has not attached one (it never stops the draw then), and the image returned is
     NoiseMonitor.denoise() of the final state instead of the plain one (needs two frame buffers); on_image
     still gets the plain images.  None leaves the function exactly as it is without it."""
@@ -1428,8 +1522,8 @@ def draw_adaptive(curr_scene: Scene, settings: render_settings, ctx: Context | N
     tighter threshold.
 
     denoise=True (the shipped parameters) or parameters as denoise_params() takes them (a dict may also hold
-    guide=True for the feature-guided filter, guide_params, and guide_samples=S for planes averaged over S rays
-    per pixel): the image returned is
+    guide=True for the feature-guided filter, guide_params, guide_samples=S for planes averaged over S rays
+    per pixel and guide_specular=... for planes that follow mirrors and glass): the image returned is
     AdaptiveAccumulator.denoise() of the final state, every pixel at its own tile's count, instead of the plain
     one (every tile needs two frame buffers); on_image still gets the plain images."""
     if settings.image_height <= 0:

@@ -1,7 +1,8 @@
 // rt_guide.hip -- the device half of the guide (include/rt_hip.h, "ray casts and feature buffers"): a validated
 // copy of the scene in device memory, the cast kernel (one lane per ray), the centre-ray pass into the feature
-// planes, the pass that averages them over a sample pattern (rt_aov.h) and their 8-bit pictures.  The first hit is rt_first_hit.h's, which the host twin (rt_guide_host.cpp)
-// compiles too.  Nothing here touches a context or the render kernels; rt_progressive.hip reads the planes
+// planes, the pass that averages them over a sample pattern (rt_aov.h), the casts and the pass that follow mirrors
+// and glass (rt_spec.h) and the planes' 8-bit pictures.  The first hit is rt_first_hit.h's, which the host twin
+// (rt_guide_host.cpp) compiles too.  Nothing here touches a context or the render kernels; rt_progressive.hip reads the planes
 // through rt_guide.h for the guided denoise.
 //
 // The scene stays in global memory; the rt_scene_soa of device pointers is a kernel argument, so its fields and
@@ -20,6 +21,7 @@
 #include "rt_first_hit.h"
 #include "rt_guide.h"
 #include "rt_quant.h"
+#include "rt_spec.h"
 
 using rtctx::DevBuf;
 using rtctx::Staged;
@@ -74,6 +76,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   coverage[p] = px.coverage;
 }
 
+// One lane per ray; a lane whose chain has ended waits for the wave's longest (rtspec::trace's do-while holds the
+// one call site of rtfh::cast).
+__global__ __launch_bounds__(kBlock) void spec_cast_kernel(const rt_scene_soa sc, const rt_spec_params sp, const float* __restrict__ rays,
+                                                          long long n, rt_guide_hit* __restrict__ hits,
+                                                          rt_spec_path* __restrict__ paths) {
+  const long long k = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= n) return;
+  rtspec::trace(sc, sp, rays + 8 * k, hits ? hits + k : nullptr, paths ? paths + k : nullptr);
+}
+
+// aov_render_kernel's lanes, loop and wave-uniform table loads, with a chain per sample (rtspec::pixel): inside a
+// sample a do-while over the chain's segments, so that the world query is inlined once for primary and
+// continuation rays; the lanes of a wave whose chains have ended wait for its longest before the next sample.
+// Four waves per SIMD, as the averaged pass: left alone the kernel takes 177 VGPRs (two waves) and is slower on
+// every scene measured; held to 128 it spills 59 VGPRs into 184 bytes of scratch.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void spec_render_kernel(
+    const rt_scene_soa sc, const rt_spec_params sp, int width, int height, int samples, int lens, const float* __restrict__ table,
+    float* __restrict__ normal, float* __restrict__ albedo, float* __restrict__ depth, int32_t* __restrict__ prim,
+    float* __restrict__ coverage) {
+  const int i = blockIdx.x * 16 + (threadIdx.x & 15), j = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (i >= width || j >= height) return;
+  rtaov::Pixel px;
+  rtspec::pixel(sc, table, samples, lens, sp, i, j, width, height, px);
+  const long long p = (long long)j * width + i;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) normal[3 * p + c] = px.n[c], albedo[3 * p + c] = px.albedo[c];
+  depth[p] = px.depth;
+  prim[p] = px.prim;
+  coverage[p] = px.coverage;
+}
+
 __global__ __launch_bounds__(kBlock) void guide_image_kernel(const float* __restrict__ plane, int normal, long long n_values,
                                                             uint8_t* __restrict__ out) {
   const long long k = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -107,11 +140,13 @@ struct RT_INTERNAL rt_guide {
   int32_t width = 0, height = 0;  // of the planes; 0 before the first render
   DevBuf<float> normal, albedo, depth;
   DevBuf<int32_t> prim;
-  DevBuf<float> coverage, table;  // rt_aov_render's: hits / samples per pixel, the pattern
-  bool averaged = false;          // the planes came from rt_aov_render
-  hipEvent_t ev[2] = {nullptr, nullptr}, aov_ev[2] = {nullptr, nullptr};
-  bool timed = false, aov_timed = false;
+  DevBuf<float> coverage, table;  // rt_aov_render's and rt_spec_render's: hits / samples per pixel, the pattern
+  bool averaged = false;          // the planes came from one of them
+  hipEvent_t ev[2] = {nullptr, nullptr}, aov_ev[2] = {nullptr, nullptr}, spec_ev[2] = {nullptr, nullptr};
+  bool timed = false, aov_timed = false, spec_timed = false;
   ~rt_guide() {
+    for (hipEvent_t e : spec_ev)
+      if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : aov_ev)
@@ -191,7 +226,8 @@ int rt_guide_create(const rt_scene_soa* scene, int hip_device, rt_guide** out) {
       (rc = upload(scene->texels, (size_t)scene->n_texels, g->texels, &g->dev.texels)))
     return rc;
   if (hipEventCreate(&g->ev[0]) != hipSuccess || hipEventCreate(&g->ev[1]) != hipSuccess ||
-      hipEventCreate(&g->aov_ev[0]) != hipSuccess || hipEventCreate(&g->aov_ev[1]) != hipSuccess)
+      hipEventCreate(&g->aov_ev[0]) != hipSuccess || hipEventCreate(&g->aov_ev[1]) != hipSuccess ||
+      hipEventCreate(&g->spec_ev[0]) != hipSuccess || hipEventCreate(&g->spec_ev[1]) != hipSuccess)
     return RT_ERR_HIP;
   *out = g.release();
   return RT_OK;
@@ -321,6 +357,74 @@ int rt_aov_coverage(rt_guide* g, float* out, int32_t png_order) {
 float rt_aov_last_ms(const rt_guide* g) {
   float ms = 0.0f;
   if (!g || !g->aov_timed || hipEventElapsedTime(&ms, g->aov_ev[0], g->aov_ev[1]) != hipSuccess) return 0.0f;
+  return ms;
+}
+
+int rt_spec_cast(rt_guide* g, const float* rays, long long n, const rt_spec_params* params, rt_guide_hit* hits, rt_spec_path* paths) {
+  if (!g || n < 0 || n > (1LL << 31)) return RT_ERR_ARG;
+  rt_spec_params p;
+  if (params) p = *params;
+  else rt_spec_params_default(&p);
+  if (!rtspec::valid(p)) return RT_ERR_ARG;
+  if (n == 0) return RT_OK;
+  if (!rays) return RT_ERR_ARG;
+  if (hipSetDevice(g->device) != hipSuccess) return RT_ERR_HIP;
+  const Staged<float> in(rays, (size_t)n * 8);
+  // an output the caller does not want is staged as one element that the kernel never sees
+  const Staged<rt_guide_hit> res(hits, hits ? (size_t)n : 1);
+  const Staged<rt_spec_path> pres(paths, paths ? (size_t)n : 1);
+  if (!in.ok() || !res.ok() || !pres.ok()) return RT_ERR_NOMEM;
+  if (in.host() && hipMemcpy(in.dev(), rays, in.bytes(), hipMemcpyHostToDevice) != hipSuccess) return RT_ERR_HIP;
+  if (hipEventRecord(g->spec_ev[0], nullptr) != hipSuccess) return RT_ERR_HIP;
+  hipLaunchKernelGGL(spec_cast_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, g->dev, p, in.dev(), n,
+                     hits ? res.dev() : nullptr, paths ? pres.dev() : nullptr);
+  if (hipGetLastError() != hipSuccess || hipEventRecord(g->spec_ev[1], nullptr) != hipSuccess ||
+      hipStreamSynchronize(nullptr) != hipSuccess)
+    return RT_ERR_HIP;
+  g->spec_timed = true;
+  int rc = RT_OK;
+  if (hits) rc = copy_out(res, hits, (size_t)n);
+  if (!rc && paths) rc = copy_out(pres, paths, (size_t)n);
+  return rc;
+}
+
+int rt_spec_render(rt_guide* g, int32_t width, int32_t height, const rt_aov_params* aov, const rt_spec_params* spec) {
+  if (!g || width < 1 || height < 1 || (long long)width * height > (1LL << 30) || (height + 15) / 16 > 65535) return RT_ERR_ARG;
+  rt_aov_params p = {1, 0, 0, 0};  // the centre ray
+  if (aov) p = *aov;
+  rt_spec_params sp;
+  if (spec) sp = *spec;
+  else rt_spec_params_default(&sp);
+  if (!rtaov::valid(p) || !rtspec::valid(sp)) return RT_ERR_ARG;
+  if (hipSetDevice(g->device) != hipSuccess) return RT_ERR_HIP;
+  const size_t px = (size_t)width * (size_t)height;
+  g->width = g->height = 0;
+  g->averaged = false;
+  if (g->normal.reserve(3 * px) == DevBuf<float>::failed || g->albedo.reserve(3 * px) == DevBuf<float>::failed ||
+      g->depth.reserve(px) == DevBuf<float>::failed || g->prim.reserve(px) == DevBuf<int32_t>::failed ||
+      g->coverage.reserve(px) == DevBuf<float>::failed ||
+      g->table.reserve((size_t)rtaov::kMaxSamples * rtaov::kEntry) == DevBuf<float>::failed)
+    return RT_ERR_NOMEM;
+  float table[rtaov::kMaxSamples * rtaov::kEntry];
+  rtaov::pattern(p, table);
+  if (hipMemcpy(g->table.get(), table, (size_t)p.samples * rtaov::kEntry * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    return RT_ERR_HIP;
+  if (hipEventRecord(g->spec_ev[0], nullptr) != hipSuccess) return RT_ERR_HIP;
+  hipLaunchKernelGGL(spec_render_kernel, dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)), dim3(256), 0, nullptr,
+                     g->dev, sp, width, height, p.samples, p.lens, g->table.get(), g->normal.get(), g->albedo.get(), g->depth.get(),
+                     g->prim.get(), g->coverage.get());
+  if (hipGetLastError() != hipSuccess || hipEventRecord(g->spec_ev[1], nullptr) != hipSuccess ||
+      hipStreamSynchronize(nullptr) != hipSuccess)
+    return RT_ERR_HIP;
+  g->spec_timed = true;
+  g->width = width, g->height = height;
+  g->averaged = true;
+  return RT_OK;
+}
+
+float rt_spec_last_ms(const rt_guide* g) {
+  float ms = 0.0f;
+  if (!g || !g->spec_timed || hipEventElapsedTime(&ms, g->spec_ev[0], g->spec_ev[1]) != hipSuccess) return 0.0f;
   return ms;
 }
 

@@ -1,5 +1,5 @@
 // rt_guide_host.cpp -- the host-only twin of the guide (rt_guide_cast_host, rt_guide_render_host, the
-// rt_guide_denoise_*_blob calls and the host-only rt_aov_* calls of include/rt_hip.h): ray casts, feature planes,
+// rt_guide_denoise_*_blob calls and the host-only rt_aov_* and rt_spec_* calls of include/rt_hip.h): ray casts, feature planes,
 // planes averaged over a sample pattern and the guided denoise of a checkpoint without a context or a GPU.  Plain C++ with no HIP include; a stand-alone program links this file
 // with rt_validate.cpp and the rt_*_blob.cpp files.
 //
@@ -8,6 +8,7 @@
 #include "rt_aov.h"
 #include "rt_denoise_math.h"
 #include "rt_first_hit.h"
+#include "rt_spec.h"
 
 namespace {
 
@@ -101,6 +102,55 @@ int rt_aov_render_host(const rt_scene_soa* scene, int32_t width, int32_t height,
     for (int32_t i = 0; i < width; ++i) {
       rtaov::Pixel px;
       rtaov::pixel(*scene, table, p.samples, p.lens, i, j, width, height, px);
+      const size_t k = (size_t)j * (size_t)width + (size_t)i;
+      for (int c = 0; c < 3; ++c) {
+        if (normal) normal[3 * k + c] = px.n[c];
+        if (albedo) albedo[3 * k + c] = px.albedo[c];
+      }
+      if (depth) depth[k] = px.depth;
+      if (prim) prim[k] = px.prim;
+      if (coverage) coverage[k] = px.coverage;
+    }
+  return RT_OK;
+}
+
+// max_fuzz: DESIGN.md 3.10.
+void rt_spec_params_default(rt_spec_params* p) {
+  if (!p) return;
+  p->max_bounces = 4;
+  p->max_fuzz = 0.1f;
+  p->glass = 1;
+  p->reserved = 0;
+}
+
+int rt_spec_cast_host(const rt_scene_soa* scene, const float* rays, long long n, const rt_spec_params* params, rt_guide_hit* hits,
+                      rt_spec_path* paths) {
+  rt_spec_params p;
+  if (params) p = *params;
+  else rt_spec_params_default(&p);
+  if (n < 0 || (n > 0 && !rays) || !rtspec::valid(p)) return RT_ERR_ARG;
+  const int rc = scene_check(scene);
+  if (rc) return rc;
+  for (long long k = 0; k < n; ++k) rtspec::trace(*scene, p, rays + 8 * k, hits ? hits + k : nullptr, paths ? paths + k : nullptr);
+  return RT_OK;
+}
+
+int rt_spec_render_host(const rt_scene_soa* scene, int32_t width, int32_t height, const rt_aov_params* aov,
+                        const rt_spec_params* spec, float* normal, float* albedo, float* depth, int32_t* prim, float* coverage) {
+  rt_aov_params p = {1, 0, 0, 0};  // the centre ray
+  if (aov) p = *aov;
+  rt_spec_params sp;
+  if (spec) sp = *spec;
+  else rt_spec_params_default(&sp);
+  if (width < 1 || height < 1 || !rtaov::valid(p) || !rtspec::valid(sp)) return RT_ERR_ARG;
+  const int rc = scene_check(scene);
+  if (rc) return rc;
+  float table[rtaov::kMaxSamples * rtaov::kEntry];
+  rtaov::pattern(p, table);
+  for (int32_t j = 0; j < height; ++j)
+    for (int32_t i = 0; i < width; ++i) {
+      rtaov::Pixel px;
+      rtspec::pixel(*scene, table, p.samples, p.lens, sp, i, j, width, height, px);
       const size_t k = (size_t)j * (size_t)width + (size_t)i;
       for (int c = 0; c < 3; ++c) {
         if (normal) normal[3 * k + c] = px.n[c];

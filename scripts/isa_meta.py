@@ -3,6 +3,8 @@ code-object metadata of a device-only assembly build of csrc/rt_kernels.hip.
 
 usage: python scripts/isa_meta.py [OUT.txt] [-DNAME ...]
   (compiles with the product flags, ~60 s)
+       python scripts/isa_meta.py --unit rt_guide.hip
+  (every kernel of another unit of csrc/, with the scalar and vector loads of its body counted)
 """
 import os
 import re
@@ -20,7 +22,30 @@ NAMED = {25730: "C2 (SPHERES|LDS|STEP)", 1112: "C3 (CORNELL)", 1560: "C4 (MESH)"
          2046: "ALL"}
 
 
+def unit(name):
+    with tempfile.TemporaryDirectory() as td:
+        s = os.path.join(td, "unit.s")
+        flags = [f for f in _build.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
+        subprocess.run(["/opt/rocm/bin/hipcc", *flags, "--cuda-device-only", "-S", "-o", s, os.path.join(_build.CSRC, name)],
+                       check=True, stderr=subprocess.DEVNULL)
+        text = open(s).read()
+    print("kernel                  vgprs  vgpr_spills  sgpr_spills  scratch_B  s_load  global_load  scratch_ops")
+    for blk in re.split(r"\n  - \.agpr_count:", text.split("amdhsa.kernels:", 1)[1]):
+        m = re.search(r"\.name:\s+(\S+)", blk)
+        if not m:
+            continue
+        g = lambda k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))  # noqa: E731
+        sym = m.group(1)
+        body = text.split(f"\n{sym}:", 1)[1].split(".Lfunc_end", 1)[0]
+        short = re.search(r"\d+([a-z_0-9]+_kernel)", sym)
+        ops = [len(re.findall(rf"\t{op}_", body)) for op in ("s_load", "global_load", "scratch")]
+        print(f"{short.group(1) if short else sym:24s}{g('vgpr_count'):5d}  {g('vgpr_spill_count'):11d}  {g('sgpr_spill_count'):11d}  "
+              f"{g('private_segment_fixed_size'):9d}  {ops[0]:6d}  {ops[1]:11d}  {ops[2]:11d}")
+
+
 def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--unit":
+        return unit(sys.argv[2])
     argv = sys.argv[1:]
     extra = [a for a in argv if a.startswith("-D")]
     argv = [a for a in argv if not a.startswith("-D")]
