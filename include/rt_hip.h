@@ -334,6 +334,13 @@ const char* rt_last_render_kernel(const rt_ctx* ctx);
 #define RT_SCHED_PROBE 4        /* items claimed longest first by a probe launch's estimate (the
                                    first launch of a configuration, options.probe_schedule)     */
 int32_t rt_last_render_schedule(const rt_ctx* ctx);
+/* Which body of render_step_kernel the last render launch ran: 1 = the plain one (the sphere stepwise
+ * variants, for a launch that splits no samples and has at most 2^32 items, width, height and fb_count
+ * at most 65536), 0 = the general one, and every other kernel.  The frame buffers do not depend on it.
+ * The general body of a variant that has both is a kernel of the same name one namespace down: rocprof
+ * lists it as "general::render_step_kernel<25730>", and rt_last_render_kernel reports the same stem for
+ * both. */
+int32_t rt_last_render_body(const rt_ctx* ctx);
 /* Audit log of the last RT_FLAG_AUDIT render: 16 floats per disagreeing BVH query (ray o[3] d[3]
  * time, tmin, tmax, culled t, culled prim (int bits), exact t, exact prim, culled rank, 0, 0).
  * Copies up to cap entries into out (may be NULL); returns the total number of disagreements. */

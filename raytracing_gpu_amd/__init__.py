@@ -246,6 +246,7 @@ ABI = {
     "rt_last_kernel_ms": (c_float, [c_void_p]),
     "rt_last_render_kernel": (ctypes.c_char_p, [c_void_p]),
     "rt_last_render_schedule": (c_int32, [c_void_p]),
+    "rt_last_render_body": (c_int32, [c_void_p]),
     "rt_audit_log": (c_int, [c_void_p, POINTER(c_float), c_int32]),
     "rt_resolve": (c_int, [c_void_p, POINTER(rt_render_args), c_void_p, c_void_p]),
     "rt_draw": (c_int, [c_void_p, POINTER(rt_render_args), POINTER(c_uint8), POINTER(rt_counters)]),
@@ -706,6 +707,10 @@ class Context:
     def last_render_schedule(self) -> int:
         """RT_SCHED_* bits of the last render launch (0: cold, nothing reused from an earlier launch)."""
         return int(lib().rt_last_render_schedule(self._c))
+
+    def last_render_body(self) -> int:
+        """Body of render_step_kernel the last render launch ran: 1 plain, 0 general (and every other kernel)."""
+        return int(lib().rt_last_render_body(self._c))
 
     def audit_log(self, cap: int = 4096) -> tuple[int, np.ndarray]:
         """(number of disagreements, [min(n, cap), 16] float32 entries) of the last audit render."""

@@ -1962,6 +1962,32 @@ constexpr int step_refill() { return (F & F_TRI) != 0 ? 4 : 1; }
 #endif
 template <int F>
 constexpr bool step_pools() { return RT_STEP_POOL != 0 && (F & F_STEP) != 0 && (F & (F_TRI | F_WORLD)) == 0; }
+// render_step_kernel's two bodies (the variants with an item pool).  A launch that splits nothing and
+// fits the pool's packed words (step_plain_launch: a function of the kernel arguments, so of the launch,
+// never of a lane or a wave) runs the PLAIN body: split_mode is the constant 0, no lane has a checkpoint
+// position (ck is always -1) and every item ends after sample spp - 1, so ck, s_end, the per-lane item
+// decode and every ckpt / contrib / cam_st / order access are compiled out and the pool refill is
+// unconditional.  In such a launch each of those values is what the general body computes at run time
+// (split_mode 0 sets ck = -1 and s_end = spp at every refill, fresh is set only with s = 0), and the
+// position -> item map, the decode arithmetic, every float operation and every RNG draw are the same
+// text, so the frame buffers are the general body's bit for bit.  What the loop then keeps in SGPRs
+// across its shading passes shrinks (<25730>: 112 -> 75 spilled SGPRs).  The general
+// body serves split launches of both modes and oversize launches.  Each body is a kernel of its own:
+// render_step_kernel<F> holds the plain one, general::render_step_kernel<F> (the same name one namespace
+// down, so every tool that matches on "render_step_kernel<F>" finds both) the general one, and
+// launch_and_record picks by step_plain_launch.  (Both bodies behind one branch in one kernel: the plain
+// half spilled more and gained less)  -DRT_STEP_PLAIN=0: the general body alone, under render_step_kernel<F>
+// (A/B, isa_same against a tree without the plain body); =2: the plain body alone (static counts;
+// rt_render refuses any other launch with RT_ERR_STATE).
+#ifndef RT_STEP_PLAIN
+#define RT_STEP_PLAIN 1
+#endif
+constexpr bool step_has_plain(int mask) {
+  return RT_STEP_PLAIN != 0 && RT_STEP_POOL != 0 && (mask & F_STEP) != 0 && (mask & (F_TRI | F_WORLD)) == 0;
+}
+__host__ __device__ __forceinline__ bool step_plain_launch(const RenderParams& P) {
+  return P.split_mode == 0 && P.total_items <= 0xffffffffull && P.W <= 65536 && P.H <= 65536 && P.fb_count <= 65536;
+}
 constexpr int kShadeMin = 60;  // render_step_kernel: default shading-phase threshold
 constexpr int kShadeMinMesh = 48;  // ... for triangle-mesh variants (round 5, with step_refill 4: C4 at
                                    // 36 / 40 / 44 / 48 / 52 / 56 / 60: 18 845 / 18 971 / 19 048 / 19 079 /
@@ -2327,514 +2353,25 @@ void render_kernel(const RenderParams P) {
 // (bvh_settle, finalize), scatter, sample / item bookkeeping, refill from the work counter,
 // the next camera ray and the next query's setup.  Per lane the sequence of RNG draws and float
 // operations is exactly render_kernel's, so frame buffers are bit-identical.
+// The kernel's text is rt_step_body.h, included once per body.
 template <int F>
 __global__ __launch_bounds__(render_block<F>()) __attribute__((amdgpu_waves_per_eu(render_wpe<F>())))
 void render_step_kernel(const RenderParams P) {
-  const DScene& S = P.S;
-  if constexpr ((F & F_LDS) != 0) stage_lds<F>(S);  // nodes, primitives, margins, materials, textures
-  if constexpr ((F & F_QLDS) != 0) {  // the quantized traversal tree (24-byte pair records)
-    uint32_t* q = (uint32_t*)rt_lds;
-    for (int k = threadIdx.x; k < 6 * S.q_pairs; k += render_block<F>()) q[k] = S.qnodes[k];
-    // ... and after its stacks the materials, textures and images (lds_mats / lds_texs / lds_imgs)
-    float4* m = rt_lds + qlds_mats_at(S);
-    const int nm = S.lds_mats, nt = 2 * S.lds_texs, ni = S.lds_imgs;
-    for (int k = threadIdx.x; k < nm + nt + ni; k += render_block<F>())
-      m[k] = k < nm ? ((const float4*)S.mats)[k]
-                    : (k < nm + nt ? ((const float4*)S.texs)[k - nm] : ((const float4*)S.images)[k - nm - nt]);
-    __syncthreads();
-  }
-  const unsigned lane = __lane_id();
-  RT_STEP_COUNT_BEGIN();
-  RT_STAMP_BEGIN();
-  const rt_object obj = ro<F>(S.objects)[ro<F>(S.world)[0]];
-  const int tbase = (F & F_WORLD) != 0 ? S.wt_fb : obj.c;  // traversal tree of the world's BVH / the world tree
-  const float tmin = 0.001f, tmax = __builtin_inff();  // render.h:63
-  long long item = -1;  // -1: no item
-  bool done = false;
-  int mode = 0;  // 0: between queries, 1: traversing, 2: search ended, shading pending
-  // Per-item / per-sample state, touched only between queries.  The world-tree variants (PKS) keep it
-  // in an LDS locker after the stacks (word k of thread t at [k * block + t]; the RNG state
-  // lane-contiguous after them) instead of VGPRs, which the traversal loop needs (C5: the variant
-  // needs ~190 VGPRs otherwise, far above the 128 of 4 waves/SIMD); their REF camera offsets come
-  // from cam_tab, as in render_kernel, instead of a camera RNG copy.
-  constexpr bool PKS = step_parks_mask(F);
-  constexpr int LB = render_block<F>();
-  uint32_t* const lk = (uint32_t*)rt_lds + LB * kStackDepth + threadIdx.x;
-  int f_r = 0, i_r = 0, r_r = 0, j_r = 0, s_r = 0, depth_r = 0, ck_r = -1, lng_r = 0, fresh_r = 0;
-  unsigned nseg_r = 0, nsamp_r = 0, item_segs_r = 0;
-  int& f = cold_ref<PKS>(f_r, lk + 0 * LB);
-  int& i = cold_ref<PKS>(i_r, lk + 1 * LB);
-  int& r = cold_ref<PKS>(r_r, lk + 2 * LB);
-  int& j = cold_ref<PKS>(j_r, lk + 3 * LB);
-  int& s = cold_ref<PKS>(s_r, lk + 4 * LB);
-  int& depth = cold_ref<PKS>(depth_r, lk + 5 * LB);
-  unsigned& item_segs = cold_ref<PKS>(item_segs_r, lk + 6 * LB);
-  unsigned& nseg = cold_ref<PKS>(nseg_r, lk + 7 * LB);
-  unsigned& nsamp = cold_ref<PKS>(nsamp_r, lk + 8 * LB);
-  int& ck = cold_ref<PKS>(ck_r, lk + 9 * LB);  // split_mode 1: perm position whose sample-start states are
-                                               // recorded; 2: split sample (the item ends after it)
-  int& lng = cold_ref<PKS>(lng_r, lk + 10 * LB);  // the item is one of the longest of the previous launch
-  int& fresh = cold_ref<PKS>(fresh_r, lk + 11 * LB);  // the item's first sample is next (camera state)
-  if constexpr (PKS) {
-    nseg = 0;
-    nsamp = 0;
-    ck = -1;
-    lng = 0;
-  }
-  float* const lkf = reinterpret_cast<float*>(lk);
-  V att_r = mk(1, 1, 1), col_r = mk(0, 0, 0);
-  auto vget = [&](V& reg, int w) -> V {
-    if constexpr (PKS) return mk(lkf[w * LB], lkf[(w + 1) * LB], lkf[(w + 2) * LB]);
-    else return reg;
-  };
-  auto vset = [&](V& reg, int w, V a) {
-    if constexpr (PKS) {
-      lkf[w * LB] = a.x;
-      lkf[(w + 1) * LB] = a.y;
-      lkf[(w + 2) * LB] = a.z;
-    } else {
-      reg = a;
-    }
-  };
-  Rng loc_r{}, cam{};
-  Rng& loc = cold_ref<PKS>(loc_r, (uint32_t*)rt_lds + LB * (kStackDepth + 18) + 6 * threadIdx.x);
-  int s_end_r = 0;  // the lane's item ends after sample s_end - 1 (spp, or one sample of a split item)
-  Ray ray{};
-  V finv = mk(0, 0, 0), oi = mk(0, 0, 0);
-  int cur = 0, sp = 0, best_prim = -1, best_rank = 0x7fffffff;
-  int pend = 0;  // deferred leaf pass: the hit leaf child this lane carries, 0: none (leaf_vote)
-  float best = 0.0f, bhi = 0.0f, second = 0.0f, qa = 0.0f, rcpa = 0.0f;
-  bool overflow = false;
-  unsigned nnode = 0, nprim = 0, nfall = 0;
-  const bool per_pixel = P.cam_mode == RT_CAM_PER_PIXEL;
-  const rt_camera& C = S.cam;
-  unsigned long long chunk_base = 0;  // wave-uniform: next unclaimed item of the wave's chunk
-  unsigned chunk_left = 0;
-  // The item pool (step_pools): lane L holds the decoded entry of position L of the wave's chunk -- the
-  // item, (f, i) and (r, j) as 16-bit halves, the slot's six state words; the last chunk_left entries
-  // (lanes kChunk - chunk_left on, positions chunk_base on) are not handed out yet.
-  constexpr bool POOL = step_pools<F>();
-  static_assert(!POOL || kChunk == 64, "the item pool holds one entry per lane");
-  uint32_t pl_item = 0, pl_fi = 0, pl_rj = 0, pl_s0 = 0, pl_s1 = 0, pl_s2 = 0, pl_s3 = 0, pl_s4 = 0, pl_s5 = 0;
-  // what the packed words hold; anything else decodes per lane (wave-uniform, constant over the launch)
-  const bool pool_fits = POOL && P.split_mode == 0 && P.total_items <= 0xffffffffull && P.W <= 65536 && P.H <= 65536 &&
-                         P.fb_count <= 65536;
-  RT_WAVE_T0();
-
-  for (;;) {
-    // Shading passes: a camera ray answered by its tile's candidate list (mode 2 right after the
-    // setup) is shaded in another pass of the same phase, so the traversal loop that follows
-    // starts with every lane traversing.
-    for (int pass = 0;; ++pass) {
-      RT_STEP_COUNT(2);
-      // ---- shading phase: finish the ended queries (render.h:60-77)
-      RT_STAMP(7);  // back-to-back pair: phase 7 = the cost of one stamp per loop trip
-      RT_STAMP(5);
-      if (mode == 2) {
-        ++nseg;
-        ++item_segs;
-        bool ended = false;
-        V contrib;
-        Hit h;
-        bool hit;
-        if constexpr ((F & F_WORLD) != 0) {
-          // list world: the tree's winner, then the constant media that follow every tree entry in
-          // the list, in list order with the closest hit so far (their RNG draws depend on it);
-          // anything uncertain -- near ties, a chain the reference may reject, a ray that could
-          // make an inert medium draw -- runs the reference's sequential list exactly
-          constexpr int FM = F & ~(F_WORLD | F_STEP | F_BVH);  // media boundaries are primitives
-          int wobj = -1, wprim = -1;
-          int st = world_settle<F>(S, ray, tmin, overflow, bhi, second, best, best_prim, best_rank, wobj, wprim, nnode);
-          if (S.w_inert && !ray_sane(ray)) st = 2;
-          const bool exact = st == 2;
-          if constexpr ((F & F_STATS) != 0) nfall += exact ? 1u : 0u;
-          hit = st == 1;
-          // exact: every entry in list order (the reference's visit sets); else the media after the tree
-          for (int w = exact ? 0 : S.w_media; w < S.n_world; ++w) {
-            const int oi = ro<F>(S.world)[w];
-            const rt_object o = ro<F>(S.objects)[oi];
-            float tq;
-            int pq;
-            bool hq;
-            const float tcl = hit ? best : tmax;
-            if (o.kind == RT_OBJ_MEDIUM) {
-              hq = object_query<FM>(S, oi, ray, tmin, tcl, tq, pq, loc, nnode, nprim, nfall);
-            } else {
-              Ray rr = ray;
-              int xi = oi;
-              if constexpr ((F & F_XFORM) != 0) if (o.kind == RT_OBJ_XFORM) {
-                Ray moved;
-                rr = xform_ray(o, ray, moved);
-                xi = o.a;
-              }
-              const rt_object x = ro<F>(S.objects)[xi];
-              if ((F & F_BVH) != 0 && x.kind == RT_OBJ_BVH) {
-                hq = bvh_exact<F>(S, x.a, x.b, rr, mk(1.0f / rr.d.x, 1.0f / rr.d.y, 1.0f / rr.d.z), tmin, tcl, tq, pq,
-                                  nnode, nprim, nfall);
-              } else {
-                pq = x.a;
-                hq = prim_t<F>(S, x.a, rr, tmin, tcl, tq, nprim);
-              }
-            }
-            if (hq) {
-              hit = true;
-              best = tq;
-              wobj = oi;
-              wprim = pq;
-            }
-          }
-          if (hit) object_record<FM>(S, wobj, wprim, ray, tmin, best, h);
-        } else {
-          hit = bvh_settle<F>(S, obj.a, obj.b, ray, tmin, tmax, overflow, bhi, second, best, best_prim, best_rank,
-                              nnode, nprim, nfall);
-          // primitive objects after the BVH in the world list (C4's ground sphere): hittable_list's
-          // rule, t_max = the closest hit so far (inclusive), so a later entry wins a tie
-          for (int w = 1; w < S.n_world; ++w) {
-            const rt_object po = ro<0>(S.objects)[ro<0>(S.world)[w]];  // uniform: scalar loads
-            float tq;
-            if (prim_t_q<F>(S, load_prim_u<F>(S, po.a), ray, tmin, hit ? best : tmax, tq, nprim)) {
-              hit = true;
-              best = tq;
-              best_prim = po.a;
-            }
-          }
-          if (hit) finalize<F>(S, best_prim, ray, tmin, best, h);
-        }
-        if (!hit) {
-          contrib = vget(att_r, 15) * ld3(S.bg);
-          ended = true;
-        } else {
-          V a, em;
-          RT_STAMP(6);
-          bool sc;
-          if constexpr (PKS) {  // on a register copy of the parked state
-            Rng lr = loc;
-            sc = scatter<F>(S, ray, h, a, em, lr);
-            loc = lr;
-          } else {
-            sc = scatter<F>(S, ray, h, a, em, loc);
-          }
-          if (sc) {
-            vset(att_r, 15, vget(att_r, 15) * a);
-            if (++depth == P.max_depth) {
-              contrib = mk(0.0f, 0.0f, 0.0f);
-              ended = true;
-            }
-          } else {
-            contrib = vget(att_r, 15) * em;
-            ended = true;
-          }
-        }
-        RT_STAMP(0);
-        if (ended) {
-          const V col = vget(col_r, 12) + contrib;
-          vset(col_r, 12, col);
-          depth = 0;
-          ++nsamp;
-          // the item ends after sample spp - 1, a split item's sample (split_mode 2) after itself
-          // (parking variants derive it from ck: sample ck % spp)
-          if constexpr (PKS) s_end_r = (P.split_mode == 2 && ck >= 0) ? ck - (ck / P.spp) * P.spp + 1 : P.spp;
-          if (++s == s_end_r) {
-            if (P.split_mode == 2 && ck >= 0) {  // one sample of a split item: its sum, merged later
-              float* dst = P.contrib + 3 * (long long)ck;
-              dst[0] = col.x;
-              dst[1] = col.y;
-              dst[2] = col.z;
-            } else {
-              const V out = (1.0f / (float)P.spp) * col;
-              float* dst = P.fb + 3 * (((long long)f * P.rows + r) * P.W + i);
-              dst[0] = out.x;
-              dst[1] = out.y;
-              dst[2] = out.z;
-            }
-            if (P.row_cost && (i & 15) == 0) atomicAdd(&P.row_cost[j], (unsigned long long)item_segs);
-            if (P.item_cost) P.item_cost[item] = (uint16_t)(item_segs < 65535u ? item_segs : 65535u);
-            if (P.split_mode == 1 && ck >= 0) P.ckpt[2 * (long long)ck * P.spp + 1] = make_uint4(0u, 0u, item_segs, 0u);
-            item = -1;
-          }
-        }
-        mode = 0;
-      }
-      RT_STAMP(8);
-      // ---- refill lanes without an item from the wave's chunk of the work counter (one atomic
-      // per kChunk items: a single counter serialises its atomics in L2)
-      const unsigned long long idle = __ballot(item < 0 && !done);
-      if (POOL && pool_fits && idle != 0) {  // (step_refill 1: at every idle lane)
-        static_assert(!POOL || step_refill<F>() == 1, "the pooled refill runs whenever a lane is idle");
-        // From the pool: the lane of rank k among the idle ones takes position chunk_base + k, as
-        // claim_items hands them out.  Every lane runs the cross-lane reads (wave-uniform control flow:
-        // ds_bpermute returns 0 from a lane that is off); at most two rounds, the second after a claim.
-        bool want = item < 0 && !done;
-        if (want) {
-          RT_STEP_COUNT(8);
-        }
-        unsigned rk = lane_rank(idle);
-        unsigned need = (unsigned)__popcll(idle);
-        for (;;) {
-          if (chunk_left == 0) {  // claim a chunk and decode it, one position per lane
-            RT_STEP_COUNT(10);
-            unsigned long long got = 0;
-            if (lane == 0) got = atomicAdd(P.work, (unsigned long long)kChunk);
-            chunk_base = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(got >> 32)) << 32) |
-                         __builtin_amdgcn_readfirstlane((unsigned)got);
-            chunk_left = kChunk;
-            const unsigned long long pos = chunk_base + lane;
-            if (pos < P.total_items) {
-              const long long it = P.perm ? (long long)P.perm[pos] : (long long)pos;
-              const long long per_row = P.per_row;  // same item order as render_kernel
-              const int qi = (int)(it / per_row);
-              const long long rem = it - (long long)qi * per_row;
-              const int2 rj = P.row_q[qi * P.pstep];
-              const int pf = (int)(rem / P.W);
-              const int pi = (int)(rem - (long long)pf * P.W) * P.pstep;
-              const long long id = P.fb_first + pf;
-              const long long p = (long long)rj.y * P.W + pi;
-              const long long slot = ((id + 1) * p + id + 1) % P.npix;  // render.h:101 (H3)
-              const uint4* st = P.states + 2 * slot;
-              const uint4 s0 = st[0], s1 = st[1];
-              pl_item = (uint32_t)it;
-              pl_fi = ((uint32_t)pf << 16) | (uint32_t)pi;
-              pl_rj = ((uint32_t)rj.x << 16) | (uint32_t)rj.y;
-              pl_s0 = s0.x; pl_s1 = s0.y; pl_s2 = s0.z; pl_s3 = s0.w; pl_s4 = s1.x; pl_s5 = s1.y;
-            }
-          }
-          const unsigned take = need < chunk_left ? need : chunk_left;
-          const int src = (int)(kChunk - chunk_left + rk);
-          const uint32_t g_item = __shfl(pl_item, src, 64), g_fi = __shfl(pl_fi, src, 64), g_rj = __shfl(pl_rj, src, 64);
-          const uint32_t g0 = __shfl(pl_s0, src, 64), g1 = __shfl(pl_s1, src, 64), g2 = __shfl(pl_s2, src, 64);
-          const uint32_t g3 = __shfl(pl_s3, src, 64), g4 = __shfl(pl_s4, src, 64), g5 = __shfl(pl_s5, src, 64);
-          if (want && rk < take) {
-            const unsigned long long pos = chunk_base + rk;
-            if (pos >= P.total_items) {
-              done = true;
-              RT_WAVE_EXHAUSTED();
-            } else {
-              item = (long long)g_item;
-              lng = pos < P.n_long ? 1 : 0;
-              f = (int)(g_fi >> 16);
-              i = (int)(g_fi & 0xffffu);
-              r = (int)(g_rj >> 16);
-              j = (int)(g_rj & 0xffffu);
-              loc.d = g0; loc.v[0] = g1; loc.v[1] = g2; loc.v[2] = g3; loc.v[3] = g4; loc.v[4] = g5;
-              s = 0;
-              s_end_r = P.spp;
-              fresh = 1;
-              depth = 0;
-              item_segs = 0;
-              col_r = mk(0, 0, 0);
-            }
-            want = false;
-          }
-          rk -= take;
-          chunk_base += take;
-          chunk_left -= take;
-          need -= take;
-          if (need == 0) break;
-        }
-      }
-      if ((!POOL || !pool_fits) && idle != 0 && (__popcll(idle) >= step_refill<F>() || __ballot(item >= 0) == 0)) {
-        const unsigned long long mine = claim_items(P.work, idle, chunk_base, chunk_left);
-        if (item < 0 && !done) {
-          RT_STEP_COUNT(8);
-          if (mine >= P.total_items) {
-            done = true;
-            RT_WAVE_EXHAUSTED();
-          } else {
-            unsigned long long pos = mine;
-            int sa = 0;
-            ck = -1;
-            if (P.split_mode == 2) {  // split samples first, then the rest of perm
-              const unsigned long long nsub = P.n_split * (unsigned long long)P.spp;
-              const unsigned long long v = P.order ? (unsigned long long)P.order[mine] : mine;
-              if (v < nsub) {
-                pos = v / (unsigned)P.spp;
-                sa = (int)(v - pos * (unsigned)P.spp);
-                ck = (int)v;
-              } else {
-                pos = v - nsub + P.n_split;
-              }
-            } else if (P.split_mode == 1 && mine < P.n_split) {
-              ck = (int)mine;
-            }
-            item = P.perm ? (long long)P.perm[pos] : (long long)pos;
-            lng = pos < P.n_long ? 1 : 0;
-            const long long per_row = P.per_row;  // same item order as render_kernel
-            const int qi = (int)(item / per_row);
-            const long long rem = item - (long long)qi * per_row;
-            const int2 rj = P.row_q[qi * P.pstep];
-            r = rj.x;
-            f = (int)(rem / P.W);
-            i = (int)(rem - (long long)f * P.W) * P.pstep;
-            j = rj.y;
-            const long long id = P.fb_first + f;
-            const long long p = (long long)j * P.W + i;
-            const long long slot = ((id + 1) * p + id + 1) % P.npix;  // render.h:101 (H3)
-            const uint4* st = sa > 0 ? P.ckpt + 2 * (long long)ck : P.states + 2 * slot;
-            const uint4 s0 = st[0], s1 = st[1];
-            loc.d = s0.x; loc.v[0] = s0.y; loc.v[1] = s0.z; loc.v[2] = s0.w; loc.v[3] = s1.x; loc.v[4] = s1.y;
-            s = sa;
-            if constexpr (!PKS) s_end_r = (P.split_mode == 2 && ck >= 0) ? sa + 1 : P.spp;
-            fresh = 1;
-            depth = 0;
-            item_segs = 0;
-            vset(col_r, 12, mk(0, 0, 0));
-          }
-        }
-      }
-      // Waves holding one of the longest items (processed first) issue ahead of the others, so the
-      // long items of a small multi-GPU share are not the last to finish.
-      if (P.n_long > 0) {
-        if (__ballot(item >= 0 && lng != 0) != 0) __builtin_amdgcn_s_setprio(3);
-        else __builtin_amdgcn_s_setprio(0);
-      }
-      // ---- next query: camera ray at a sample's start (render.h:105-108, camera.h:49-58)
-      RT_STAMP(1);
-      if (item >= 0 && mode == 0) {
-        // camera ray: its tile's candidate list (count + first entries) is loaded before the ray is
-        // generated, so the loads overlap the camera arithmetic
-        const bool listed = (F & F_WORLD) == 0 && depth == 0 && P.tile_cnt != nullptr;
-        const int32_t* ent = nullptr;
-        int tcnt = -1;
-        int4 g0 = make_int4(0, 0, 0, 0);
-        if (listed) {
-          const int t = (j >> kTileShift) * P.tiles_x + (i >> kTileShift);
-          ent = P.tile_ent + (size_t)t * P.tile_cap * 2;  // (id, nearest) pairs
-          tcnt = P.tile_cnt[t];
-          g0 = *reinterpret_cast<const int4*>(ent);
-        }
-        if (depth == 0 && PKS) {
-          if (P.split_mode == 1 && ck >= 0 && s > 0) {  // record the sample-start state for split launches
-            uint4* dst = P.ckpt + 2 * ((long long)ck * P.spp + s);
-            dst[0] = make_uint4(loc.d, loc.v[0], loc.v[1], loc.v[2]);
-            dst[1] = make_uint4(loc.v[3], loc.v[4], item_segs, 0u);
-          }
-          Rng lr = loc;
-          camera_ray(P, C, i, j, s, per_pixel, lr, ray);  // REF offsets from cam_tab
-          loc = lr;
-          vset(att_r, 15, mk(1.0f, 1.0f, 1.0f));
-        } else if (depth == 0) {
-          // REF: the step kernel draws the per-sample lens offset and time from its own copy of the
-          // pristine slot-0 state instead of cam_tab (measured faster here: the table read would sit
-          // in the shading phase's dependent chain)
-          if (fresh && !per_pixel) {
-            if (s == 0) {
-              cam.d = P.cam_state[0];
-              for (int k = 0; k < 5; ++k) cam.v[k] = P.cam_state[1 + k];
-            } else {  // a split sample: the camera state at its start
-              const uint4 c0 = P.cam_st[2 * s], c1 = P.cam_st[2 * s + 1];
-              cam.d = c0.x; cam.v[0] = c0.y; cam.v[1] = c0.z; cam.v[2] = c0.w; cam.v[3] = c1.x; cam.v[4] = c1.y;
-            }
-          }
-          fresh = 0;
-          if (P.split_mode == 1 && ck >= 0 && s > 0) {  // record the sample-start state for split launches
-            uint4* dst = P.ckpt + 2 * ((long long)ck * P.spp + s);
-            dst[0] = make_uint4(loc.d, loc.v[0], loc.v[1], loc.v[2]);
-            dst[1] = make_uint4(loc.v[3], loc.v[4], item_segs, 0u);
-          }
-          const float u = ((float)i + rtx::uniform(loc)) / (float)P.W;
-          const float v = ((float)j + rtx::uniform(loc)) / (float)P.H;
-          Rng& cr = per_pixel ? loc : cam;
-          const V rd = C.lens_radius * in_unit_disk(cr);
-          const V off = rd.x * ld3(C.u) + rd.y * ld3(C.v);
-          ray.o = ld3(C.origin) + off;
-          ray.d = ld3(C.lower_left) + u * ld3(C.horizontal) + v * ld3(C.vertical) - ld3(C.origin) - off;
-          ray.tm = urange(cr, C.time0, C.time1);
-          vset(att_r, 15, mk(1.0f, 1.0f, 1.0f));
-        }
-        // traversal reciprocals: hardware v_rcp_f32 (1 ulp; the tree's boxes are padded by 2^-16
-        // relative, far above either reciprocal's rounding) instead of three IEEE divides
-        const V inv = mk(__builtin_amdgcn_rcpf(ray.d.x), __builtin_amdgcn_rcpf(ray.d.y), __builtin_amdgcn_rcpf(ray.d.z));
-        finv = mk(__builtin_fminf(__builtin_fmaxf(inv.x, -1e30f), 1e30f),
-                  __builtin_fminf(__builtin_fmaxf(inv.y, -1e30f), 1e30f),
-                  __builtin_fminf(__builtin_fmaxf(inv.z, -1e30f), 1e30f));
-        oi = mk(ray.o.x * finv.x, ray.o.y * finv.y, ray.o.z * finv.z);
-        qa = len2(ray.d);
-        rcpa = __builtin_amdgcn_rcpf(qa);
-        best = __builtin_inff();
-        bhi = __builtin_inff();
-        second = __builtin_inff();
-        best_prim = -1;
-        best_rank = 0x7fffffff;
-        cur = 0;
-        sp = 0;
-        overflow = false;
-        mode = 1;
-        if constexpr ((F & F_WORLD) == 0) {
-          if (listed && tcnt >= 0) {  // camera ray: the tile's candidate list instead of the tree
-            tile_candidates<F>(S, ent, tcnt, g0, ray, qa, rcpa, tmin, tmax, best, bhi, second, best_prim, best_rank,
-                               nprim);
-            mode = 2;
-          }
-        }
-      }
-      if (pass + 1 >= kShadePasses || __ballot(mode == 2) == 0) break;
-    }
-    RT_STAMP(3);
-    if (__ballot(mode != 0) == 0) break;  // no item left for any lane of the wave (mode 2: a listed camera ray)
-    // ---- traversal steps until shade_min lanes wait (or none traverses)
-    for (;;) {
-      RT_STEP_COUNT(3);
-      // several traversal steps per check of the shading condition, same VGPRs (same box, Mrays/s at
-      // 1 / 2 / 3 / 4 steps: C2 14 538 / 14 713 / 14 829 / 14 843, C4 11 180 / 11 247 (before the
-      // triangle dedupe) and 14 095 / 14 051 / 13 990 after it); the opt-in world-tree variants keep
-      // one (more spills with two)
-      // (with the deferred leaf pass, C2 at 2 / 4 / 6 / 8 steps: 16.10 / 15.82 / 15.87 / 15.99 ms)
-      constexpr int kUnroll = (F & F_WORLD) != 0 ? 1 : ((F & F_TRI) != 0 ? 2 : 4);
-      if constexpr (leaf_pass_min(F) > 0) {
-        // deferred leaf pass (leaf_vote): a lane whose search ends holding a leaf waits like any
-        // other, and a flush pass before the shading phase tests every leaf still held, so no lane
-        // settles with a leaf untested and `pend` is not live across the phase
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-          int n0 = 0, n1 = 0;
-          if (mode == 1) {
-            RT_STEP_COUNT(0);
-            if (!trav_node<F>(S, tbase, oi, finv, tmin, tmax, bhi, cur, sp, overflow, nnode, n0, n1)) mode = 2;
-          }
-          leaf_vote<F>(S, false, pend, n0, n1, ray, qa, rcpa, tmin, tmax, best, bhi, second, best_prim, best_rank,
-                       nprim);
-        }
-        // (the threshold as a kernel argument measured 1.5 % faster than the compile-time constant)
-        if (__ballot(mode == 1) == 0 || __popcll(__ballot(mode == 2)) >= P.shade_min) {
-          leaf_vote<F>(S, true, pend, 0, 0, ray, qa, rcpa, tmin, tmax, best, bhi, second, best_prim, best_rank,
-                       nprim);
-          break;
-        }
-      } else {
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u)
-        if (mode == 1) {
-          RT_STEP_COUNT(0);
-          if (!trav_step<F>(S, tbase, ray, oi, finv, qa, rcpa, tmin, tmax, cur, sp, best, bhi, second, best_prim,
-                            best_rank, overflow, nnode, nprim))
-            mode = 2;
-        }
-        // (the threshold as a kernel argument measured 1.5 % faster than the compile-time constant)
-        if (__ballot(mode == 1) == 0 || __popcll(__ballot(mode == 2)) >= P.shade_min) break;
-      }
-    }
-  }
-
-  RT_STEP_COUNT_END();
-  RT_STAMP_END();
-  RT_WAVE_END();
-  const unsigned long long ws = wave_sum(nseg), wm = wave_sum(nsamp);
-  unsigned long long wn = 0, wp = 0, wf = 0;
-  if constexpr ((F & F_STATS) != 0) {
-    wn = wave_sum(nnode);
-    wp = wave_sum(nprim);
-    wf = wave_sum(nfall);
-  }
-  if (lane == 0) {
-    atomicAdd(&P.counters[0], ws);
-    atomicAdd(&P.counters[3], wm);
-    if constexpr ((F & F_STATS) != 0) {
-      atomicAdd(&P.counters[1], wn);
-      atomicAdd(&P.counters[2], wp);
-      atomicAdd(&P.counters[4], wf);
-    }
-  }
+#define RT_STEP_BODY_PLAIN step_has_plain(F)
+#include "rt_step_body.h"
+#undef RT_STEP_BODY_PLAIN
 }
+#if RT_STEP_PLAIN == 1
+namespace general {
+template <int F>
+__global__ __launch_bounds__(render_block<F>()) __attribute__((amdgpu_waves_per_eu(render_wpe<F>())))
+void render_step_kernel(const RenderParams P) {
+#define RT_STEP_BODY_PLAIN false
+#include "rt_step_body.h"
+#undef RT_STEP_BODY_PLAIN
+}
+}  // namespace general
+#endif
 
 // curand_init(seed, slot, 0) for every slot < n (render.h:84-92).  Each lane owns `chunk`
 // consecutive slots: one seed scramble + subsequence jump A^(first * 2^67) applied digit by digit
@@ -3278,6 +2815,7 @@ struct rt_ctx : StreamOwner {
   float last_kernel_ms = 0.0f;  // ... its render kernel (and split merge) alone
   int last_sched = 0;  // RT_SCHED_* of the last render launch
   char last_kernel[48] = "";  // rocprof name stem of the last render launch, e.g. render_step_kernel<25730>
+  int last_body = 0;  // ... and the body it ran: 1 = render_step_kernel's plain body (RT_STEP_PLAIN), 0 = the general one
   DevBuf<float> dbg;  // audit log: [0] = count, then 16 floats per entry
   // Camera-ray candidate lists (world = one BVH): bounding spheres of the world BVH's primitives
   // over the shutter (scene buffers) and the per-tile lists of the last (scene, W, H).
@@ -3298,9 +2836,17 @@ namespace {
 struct Variant {
   int mask;
   const void* fn;
+  const void* fn_general;  // render_step_kernel's general body where the variant has two (RT_STEP_PLAIN), else null
 };
-#define RT_VARIANT(m) {m, (const void*)render_kernel<m>}
-#define RT_VARIANT_STEP(m) {m, (const void*)render_step_kernel<m>}
+template <int M>
+const void* step_general_fn() {
+#if RT_STEP_PLAIN == 1
+  if constexpr (step_has_plain(M)) return (const void*)general::render_step_kernel<M>;
+#endif
+  return nullptr;
+}
+#define RT_VARIANT(m) {m, (const void*)render_kernel<m>, nullptr}
+#define RT_VARIANT_STEP(m) {m, (const void*)render_step_kernel<m>, step_general_fn<m>()}
 const Variant kVariants[] = {
     RT_VARIANT_STEP(F_SPHERES | F_LDS | F_STEP),
     RT_VARIANT_STEP(F_SPHERES | F_STEP),
@@ -4353,7 +3899,10 @@ int probe_launch(rt_ctx* c, const Launch& L, const KernelChoice& K, RenderParams
   Q.row_cost = nullptr;
   Q.split_mode = 0;
   void* qargs[] = {&Q};
-  HIPCHK(c, hipLaunchKernel(kVariants[probe_variant(K.var)].fn, dim3(K.blocks), dim3(K.bs), qargs, K.shmem, c->stream));
+  const Variant& pv = kVariants[probe_variant(K.var)];  // (a probe splits nothing; an oversize one is general)
+  const void* pfn = !step_has_plain(pv.mask) || step_plain_launch(Q) ? pv.fn : pv.fn_general;
+  if (!pfn) return fail(c, RT_ERR_STATE, "this build (RT_STEP_PLAIN=2) has the plain body only: no oversize launches");
+  HIPCHK(c, hipLaunchKernel(pfn, dim3(K.blocks), dim3(K.bs), qargs, K.shmem, c->stream));
   HIPCHK(c, hipGetLastError());
   RT_DIAG_PROBE_COSTS(c, L.pitems);  // diagnostic builds only (rt_diag.h): the raw probe counts to a file
   probe_smooth_kernel<<<(unsigned)((L.pitems + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
@@ -4386,9 +3935,13 @@ int launch_and_record(rt_ctx* c, const Launch& L, const KernelChoice& K, RenderP
   RT_STAMP_HOST_RESET();
   RT_WAVE_HOST_RESET();
   void* kargs[] = {&P};
+  // render_step_kernel's body for these arguments: the variant's own kernel holds the plain one
+  const bool plain = step_has_plain(K.mask) && step_plain_launch(P);
+  const void* fn = plain || !step_has_plain(K.mask) ? kVariants[K.var].fn : kVariants[K.var].fn_general;
+  if (!fn) return fail(c, RT_ERR_STATE, "this build (RT_STEP_PLAIN=2) has the plain body only: no split or oversize launches");
   // rt_last_kernel_ms: the render kernel (and the split merge), not the probe before it
   HIPCHK(c, hipEventRecord(c->ev2, c->stream));
-  HIPCHK(c, hipLaunchKernel(kVariants[K.var].fn, dim3(K.blocks), dim3(K.bs), kargs, K.shmem, c->stream));
+  HIPCHK(c, hipLaunchKernel(fn, dim3(K.blocks), dim3(K.bs), kargs, K.shmem, c->stream));
   HIPCHK(c, hipGetLastError());
   if (L.split_mode == 2) {
     merge_split_kernel<<<(unsigned)((c->n_split + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(P);
@@ -4399,6 +3952,7 @@ int launch_and_record(rt_ctx* c, const Launch& L, const KernelChoice& K, RenderP
                   (L.probe ? RT_SCHED_PROBE : 0);
   snprintf(c->last_kernel, sizeof(c->last_kernel), "%s<%d>",
            (K.mask & F_STEP) != 0 ? "render_step_kernel" : "render_kernel", K.mask);
+  c->last_body = plain ? 1 : 0;
   unsigned long long host_cnt[8];
   HIPCHK(c, hipMemcpyAsync(host_cnt, c->work.get(), sizeof(host_cnt), hipMemcpyDeviceToHost, c->stream));
   std::vector<unsigned long long> cost(L.measure_rows ? (size_t)a->height : 0);
@@ -4479,6 +4033,7 @@ float rt_last_render_ms(const rt_ctx* c) { return c ? c->last_ms : 0.0f; }
 float rt_last_kernel_ms(const rt_ctx* c) { return c ? c->last_kernel_ms : 0.0f; }
 const char* rt_last_render_kernel(const rt_ctx* c) { return c ? c->last_kernel : ""; }
 int32_t rt_last_render_schedule(const rt_ctx* c) { return c ? c->last_sched : 0; }
+int32_t rt_last_render_body(const rt_ctx* c) { return c ? c->last_body : 0; }
 
 int rt_read_states(rt_ctx* c, int64_t first, int64_t count, uint32_t* out) {
   if (!c || !out || first < 0 || count < 0) return fail(c, RT_ERR_ARG, "bad read_states args");

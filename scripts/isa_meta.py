@@ -64,14 +64,16 @@ def main():
         g = lambda k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))  # noqa: E731
         mask = int(re.search(r"ILi(\d+)E", m.group(1)).group(1))
         kind = "render_step_kernel" if "step" in m.group(1) else "render_kernel"
+        if "7general" in m.group(1):  # the general body's kernel of a variant that has two (RT_STEP_PLAIN)
+            kind = "general::" + kind
         feats = "|".join(v for b, v in FEAT.items() if mask >> b & 1)
         rows.append((kind, mask, g("vgpr_count"), g("vgpr_spill_count"), g("sgpr_spill_count"),
                      g("private_segment_fixed_size"), NAMED.get(mask & ~1, ""), feats))
     rows.sort(key=lambda r: (r[0], r[1]))
     out = [f"# build_id {_build.kernel_build_id()}",
-           "kernel                      vgprs  vgpr_spills  sgpr_spills  scratch_B  config  features"]
+           "kernel                               vgprs  vgpr_spills  sgpr_spills  scratch_B  config  features"]
     for k, mask, v, vs, ss, priv, cfg, feats in rows:
-        out.append(f"{k + '<' + str(mask) + '>':28s}{v:5d}  {vs:11d}  {ss:11d}  {priv:9d}  {cfg:22s}  {feats}")
+        out.append(f"{k + '<' + str(mask) + '>':37s}{v:5d}  {vs:11d}  {ss:11d}  {priv:9d}  {cfg:22s}  {feats}")
     txt = "\n".join(out) + "\n"
     if len(sys.argv) > 1:
         open(sys.argv[1], "w").write(txt)
