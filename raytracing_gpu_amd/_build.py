@@ -1,7 +1,8 @@
 """Build helpers: compile the gfx950 HIP library and the CPU oracle in-tree.
 
 `build_hip()` produces raytracing_gpu_amd/librt_hip.so (hipcc --offload-arch=gfx950, host + device
-code).  `build_oracle()` runs oracle/Makefile (test infrastructure only).
+code).  `build_oracle()` runs oracle/Makefile and `build_devprobe()` compiles the device probe of the shared
+arithmetic headers (both test infrastructure only).
 """
 from __future__ import annotations
 
@@ -116,9 +117,31 @@ def build_oracle(force: bool = False) -> str:
     return os.path.join(odir, "_build", "libref_cpu.so")
 
 
+def build_devprobe(force: bool = False, verbose: bool = False) -> str:
+    """oracle/_build/librt_devprobe.so (test infrastructure): the shared arithmetic headers of csrc/ one value
+    at a time, on the device and in hipcc's host pass (oracle/devprobe/rt_devprobe.hip), compiled with the
+    library's own HIPCC_FLAGS so that it probes the code generation the kernels get."""
+    pdir = os.path.join(ROOT, "oracle", "devprobe")
+    out = os.path.join(ROOT, "oracle", "_build", "librt_devprobe.so")
+    src = os.path.join(pdir, "rt_devprobe.hip")
+    deps = [src, os.path.join(pdir, "rt_devprobe_fns.h"), os.path.join(ROOT, "include", "rt_hip.h")]
+    deps += [os.path.join(CSRC, f) for f in ("rt_detmath.h", "rt_xorwow.h", "rt_quant.h", "rt_denoise_math.h")]
+    if not force and not _stale(out, deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, *HIPCC_FLAGS, "-I" + CSRC, "-o", out + ".tmp", src]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=pdir)
+    os.replace(out + ".tmp", out)
+    return out
+
+
 if __name__ == "__main__":
     build_hip(force="--force" in sys.argv, verbose=True)
     build_multi(force="--force" in sys.argv, verbose=True)
     build_examples(force="--force" in sys.argv, verbose=True)
     build_oracle(force="--force" in sys.argv)
+    build_devprobe(force="--force" in sys.argv, verbose=True)
     print(LIB)

@@ -6,7 +6,7 @@ Context.last_render_body() says which (1 plain, 0 general).  Which body runs mus
 big1 at depth 50, seed 1984, and compares every float of every frame buffer with the CPU oracle bit for
 bit, with the oracle's segment count over the rendered pixels and the sample count.
 
-Not tested: fb_count > 65536 and more than 2^32 items.  Such a launch is hours long.
+Not tested: more than 2^32 items.  Such a launch is hours long.
 """
 import functools
 
@@ -153,6 +153,44 @@ def test_the_pool_words_hold_16_bits(rtlib, gpu_ctx, oracle, shape, body):
     assert gpu_ctx.last_render_kernel() == "render_step_kernel<25730>"
     assert gpu_ctx.last_render_body() == body
     _check(got, rows, cnt, W, H, 1, 1, REF)
+
+
+@functools.lru_cache(maxsize=None)
+def _want_2x1(nfb):
+    """The oracle's 2 x 1 frame buffers 0 .. nfb - 1 at spp 1 ([nfb][1][2][3]) and their segments ([nfb])."""
+    from oracle import ref_cpu
+
+    ref = ref_cpu.RefScene("big1")
+    fbs, segs = np.empty((nfb, 1, 2, 3), np.float32), np.empty(nfb, np.int64)
+    for f in range(nfb):
+        fb, c, _ = ref.render(2, 1, 1, f, 50, REF)
+        fbs[f], segs[f] = fb.reshape(1, 2, 3), c["segments"]
+    return fbs, segs
+
+
+def test_the_pool_words_hold_16_bits_of_the_frame_buffer(rtlib, gpu_ctx, oracle):
+    """The other half of the word that holds the column: a frame-buffer index of 65535 is the last one it
+    holds, so fb_count 65536 is plain and 65537 general.  A 2 x 1 image at spp 1 in natural order keeps such a
+    launch at 131 074 items.  The launches agree bit for bit on the 65536 buffers they share; buffers 0, 1,
+    4099 k, 65534, 65535 and 65536 (and, the oracle being quick at this size, every other one) are the
+    oracle's, with its segment count."""
+    W, H, N = 2, 1, 65536
+    gpu_ctx.upload(rtlib.Scene.builtin("big1"))
+    plain, rows, cnt_p = _launch(rtlib, gpu_ctx, W, H, 1, N, REF, schedule=False)
+    assert gpu_ctx.last_render_kernel() == "render_step_kernel<25730>"
+    assert gpu_ctx.last_render_body() == PLAIN
+    general, rows_g, cnt_g = _launch(rtlib, gpu_ctx, W, H, 1, N + 1, REF, schedule=False)
+    assert gpu_ctx.last_render_kernel() == "render_step_kernel<25730>"
+    assert gpu_ctx.last_render_body() == GENERAL
+    assert list(rows) == [0] and list(rows_g) == [0]
+    assert np.array_equal(_bits(plain), _bits(general[:N])), "the bodies differ on the buffers they share"
+    want, segs = _want_2x1(N + 1)
+    listed = [0, 1] + list(range(4099, N, 4099)) + [N - 2, N - 1, N]
+    for f in listed:
+        assert np.array_equal(_bits(general[f]), _bits(want[f])), f"fb {f} differs from the oracle"
+    assert np.array_equal(_bits(general), _bits(want))
+    assert cnt_p["segments"] == int(segs[:N].sum()) and cnt_g["segments"] == int(segs.sum())
+    assert cnt_p["samples"] == N * W * H and cnt_g["samples"] == (N + 1) * W * H
 
 
 # ---------------------------------------------------------------- 3. general launches stay general
