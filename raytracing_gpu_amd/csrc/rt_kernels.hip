@@ -1905,13 +1905,13 @@ struct RenderParams {
   const uint32_t* perm;
   uint16_t* item_cost;
   unsigned long long n_long;
-  uint32_t cam_state[6];  // pristine slot-0 state curand_init(seed, 0, 0): REF camera draws of render_step_kernel
+  uint32_t cam_state[6];  // pristine slot-0 state curand_init(seed, 0, 0): REF camera draws of render_step_kernel's mesh variants
   // Split samples (render_step_kernel, warm launches of a small share; see rt_render): the first
   // n_split positions of perm are the longest items.  split_mode 1: those items record their RNG
   // state at every sample start into ckpt[pos * spp + s]; split_mode 2: their samples are separate
   // work items (claim k < n_split * spp: position k / spp, sample k % spp) that start from ckpt
   // (sample 0: from states) and write the sample's sum to contrib[3 k]; merge_split_kernel adds
-  // them up in sample order.  cam_st[s]: the REF camera state at sample s's start.  order (split_mode
+  // them up in sample order.  cam_st[s]: the REF camera state at sample s's start (the mesh variants; the others read cam_tab[s]).  order (split_mode
   // 2, may be null): claim k takes order[k] instead of k -- split samples and the other items in
   // one longest-first sequence by the recording launch's per-sample segment counts (split_mode 1
   // keeps them in ckpt's spare word: segments before sample s at [pos * spp + s], the item's
@@ -1988,6 +1988,12 @@ constexpr bool step_has_plain(int mask) {
 __host__ __device__ __forceinline__ bool step_plain_launch(const RenderParams& P) {
   return P.split_mode == 0 && P.total_items <= 0xffffffffull && P.W <= 65536 && P.H <= 65536 && P.fb_count <= 65536;
 }
+// render_step_kernel's sphere variants (<25730>, <25731>, <287874>, <17538>).  In the REF camera mode they
+// read the lens offset and time of sample s from cam_tab[s] (camera_table, built by the host with the same
+// float operations), as camera_ray does: a lane then holds no second RNG state and no wave runs
+// in_unit_disk's rejection loop until its slowest lane accepts.  The mesh variants keep
+// their copy of the pristine slot-0 state (P.cam_state, P.cam_st).
+constexpr bool step_sphere(int mask) { return (mask & F_STEP) != 0 && (mask & (F_TRI | F_WORLD)) == 0; }
 constexpr int kShadeMin = 60;  // render_step_kernel: default shading-phase threshold
 constexpr int kShadeMinMesh = 48;  // ... for triangle-mesh variants (round 5, with step_refill 4: C4 at
                                    // 36 / 40 / 44 / 48 / 52 / 56 / 60: 18 845 / 18 971 / 19 048 / 19 079 /
@@ -2079,6 +2085,24 @@ constexpr bool launders() { return (F & (F_BVH | F_TRI)) == 0; }
 template <int F>
 __device__ __forceinline__ const RenderParams& loop_params(const RenderParams& P0) {
   if constexpr (launders<F>()) {
+    const RT_RO RenderParams* p = (const RT_RO RenderParams*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const RenderParams*)p;
+  } else {
+    return P0;
+  }
+}
+// render_step_kernel's shading passes: the same opaque pointer, taken at the head of each pass and used for
+// the arguments that only the passes read (rt_step_body.h), in the sphere variants.  loop_params in this
+// kernel re-read every argument in every trip and put the reloads into the traversal chain (6.5 % slower);
+// here the traversal loop's own arguments stay in SGPRs and the others stop being parked in lanes across it
+// (DESIGN.md 3.1j).  -DRT_STEP_SHADE_ARGS=0: no variant (A/B); 1: the plain body only; 2: both bodies.
+#ifndef RT_STEP_SHADE_ARGS
+#define RT_STEP_SHADE_ARGS 2
+#endif
+template <int F, bool PLAIN>
+__device__ __forceinline__ const RenderParams& shade_params(const RenderParams& P0) {
+  if constexpr (step_sphere(F) && (RT_STEP_SHADE_ARGS == 2 || (RT_STEP_SHADE_ARGS == 1 && PLAIN))) {
     const RT_RO RenderParams* p = (const RT_RO RenderParams*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));
     return *(const RenderParams*)p;

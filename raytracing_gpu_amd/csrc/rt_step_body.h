@@ -35,7 +35,8 @@
   // in an LDS locker after the stacks (word k of thread t at [k * block + t]; the RNG state
   // lane-contiguous after them) instead of VGPRs, which the traversal loop needs (C5: the variant
   // needs ~190 VGPRs otherwise, far above the 128 of 4 waves/SIMD); their REF camera offsets come
-  // from cam_tab, as in render_kernel, instead of a camera RNG copy.
+  // from cam_tab, as in render_kernel, instead of a camera RNG copy, and so do the sphere variants'
+  // (TAB below).
   constexpr bool PKS = step_parks_mask(F);
   constexpr int LB = render_block<F>();
   uint32_t* const lk = (uint32_t*)rt_lds + LB * kStackDepth + threadIdx.x;
@@ -53,7 +54,7 @@
   int& ck = cold_ref<PKS>(ck_r, lk + 9 * LB);  // split_mode 1: perm position whose sample-start states are
                                                // recorded; 2: split sample (the item ends after it)
   int& lng = cold_ref<PKS>(lng_r, lk + 10 * LB);  // the item is one of the longest of the previous launch
-  int& fresh = cold_ref<PKS>(fresh_r, lk + 11 * LB);  // the item's first sample is next (camera state)
+  int& fresh = cold_ref<PKS>(fresh_r, lk + 11 * LB);  // the item's first sample is next (camera state; !TAB)
   if constexpr (PKS) {
     nseg = 0;
     nsamp = 0;
@@ -86,7 +87,6 @@
   bool overflow = false;
   unsigned nnode = 0, nprim = 0, nfall = 0;
   const bool per_pixel = P.cam_mode == RT_CAM_PER_PIXEL;
-  const rt_camera& C = S.cam;
   unsigned long long chunk_base = 0;  // wave-uniform: next unclaimed item of the wave's chunk
   unsigned chunk_left = 0;
   // The item pool (step_pools): lane L holds the decoded entry of position L of the wave's chunk -- the
@@ -99,14 +99,28 @@
   const bool pool_fits = PLAIN || (POOL && step_plain_launch(P));
   // split state: no lane of a plain launch has any
   constexpr bool SPLIT = !PLAIN;
+  // REF camera of the sphere variants (step_sphere): the lens offset and time of sample s from cam_tab[s],
+  // as in camera_ray, so these variants hold neither `cam` nor `fresh` and run no disk loop in REF mode.
+  // The entry is read where s is set (the sample end, the hand-out of an item), ahead of the refill; the
+  // camera setup of the same pass consumes it (cam_e).
+  constexpr bool TAB = step_sphere(F);
   RT_WAVE_T0();
 
+  const RenderParams& P0 = P;
   for (;;) {
     // Shading passes: a camera ray answered by its tile's candidate list (mode 2 right after the
     // setup) is shaded in another pass of the same phase, so the traversal loop that follows
     // starts with every lane traversing.
     for (int pass = 0;; ++pass) {
+      // The arguments that only the shading passes read (the frame buffer and its layout, spp, max_depth,
+      // the image size, the background, the tile lists, the camera, the work counter and the item decode's
+      // words, the optional pointers) are re-read from the argument segment where a pass uses them, in the
+      // variants of shade_params, instead of being parked in lanes across the traversal loop.  What the
+      // traversal steps read too stays in SGPRs: S (the scene's pointers and LDS offsets), tbase, shade_min.
+      const RenderParams& P = shade_params<F, PLAIN>(P0);
+      const rt_camera& C = P.S.cam;
       RT_STEP_COUNT(2);
+      float4 cam_e = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // TAB: cam_tab[s] of a lane whose sample starts in this pass
       // ---- shading phase: finish the ended queries (render.h:60-77)
       RT_STAMP(7);  // back-to-back pair: phase 7 = the cost of one stamp per loop trip
       RT_STAMP(5);
@@ -181,7 +195,7 @@
           if (hit) finalize<F>(S, best_prim, ray, tmin, best, h);
         }
         if (!hit) {
-          contrib = vget(att_r, 15) * ld3(S.bg);
+          contrib = vget(att_r, 15) * ld3(P.S.bg);
           ended = true;
         } else {
           V a, em;
@@ -214,7 +228,9 @@
           // the item ends after sample spp - 1, a split item's sample (split_mode 2) after itself
           // (parking variants derive it from ck: sample ck % spp)
           if constexpr (PKS) s_end_r = (P.split_mode == 2 && ck >= 0) ? ck - (ck / P.spp) * P.spp + 1 : P.spp;
-          if (++s == (PLAIN ? P.spp : s_end_r)) {
+          const bool item_ends = ++s == (PLAIN ? P.spp : s_end_r);
+          if (TAB && !per_pixel && !item_ends) cam_e = P.S.cam_tab[s];  // the next sample's, below spp
+          if (item_ends) {
             if (SPLIT && P.split_mode == 2 && ck >= 0) {  // one sample of a split item: its sum, merged later
               float* dst = P.contrib + 3 * (long long)ck;
               dst[0] = col.x;
@@ -298,7 +314,8 @@
               loc.d = g0; loc.v[0] = g1; loc.v[1] = g2; loc.v[2] = g3; loc.v[3] = g4; loc.v[4] = g5;
               s = 0;
               if constexpr (!PLAIN) s_end_r = P.spp;
-              fresh = 1;
+              if constexpr (!TAB) fresh = 1;
+              if (TAB && !per_pixel) cam_e = P.S.cam_tab[0];
               depth = 0;
               item_segs = 0;
               col_r = mk(0, 0, 0);
@@ -354,7 +371,8 @@
             loc.d = s0.x; loc.v[0] = s0.y; loc.v[1] = s0.z; loc.v[2] = s0.w; loc.v[3] = s1.x; loc.v[4] = s1.y;
             s = sa;
             if constexpr (!PKS) s_end_r = (P.split_mode == 2 && ck >= 0) ? sa + 1 : P.spp;
-            fresh = 1;
+            if constexpr (!TAB) fresh = 1;
+            if (TAB && !per_pixel) cam_e = P.S.cam_tab[sa];  // (a split sample needs no camera state)
             depth = 0;
             item_segs = 0;
             vset(col_r, 12, mk(0, 0, 0));
@@ -392,22 +410,35 @@
           camera_ray(P, C, i, j, s, per_pixel, lr, ray);  // REF offsets from cam_tab
           loc = lr;
           vset(att_r, 15, mk(1.0f, 1.0f, 1.0f));
+        } else if (TAB && depth == 0) {
+          // camera_ray's text with the table entry read ahead; PER_PIXEL draws from loc exactly as the
+          // branch below does (jitter, disk, time: render.h:105-108 order)
+          if (SPLIT && P.split_mode == 1 && ck >= 0 && s > 0) {  // record the sample-start state for split launches
+            uint4* dst = P.ckpt + 2 * ((long long)ck * P.spp + s);
+            dst[0] = make_uint4(loc.d, loc.v[0], loc.v[1], loc.v[2]);
+            dst[1] = make_uint4(loc.v[3], loc.v[4], item_segs, 0u);
+          }
+          const float u = ((float)i + rtx::uniform(loc)) / (float)P.W;
+          const float v = ((float)j + rtx::uniform(loc)) / (float)P.H;
+          V off;
+          if (per_pixel) {
+            const V rd = C.lens_radius * in_unit_disk(loc);
+            off = rd.x * ld3(C.u) + rd.y * ld3(C.v);
+            ray.tm = urange(loc, C.time0, C.time1);
+          } else {
+            off = mk(cam_e.x, cam_e.y, cam_e.z);
+            ray.tm = cam_e.w;
+          }
+          ray.o = ld3(C.origin) + off;
+          ray.d = ld3(C.lower_left) + u * ld3(C.horizontal) + v * ld3(C.vertical) - ld3(C.origin) - off;
+          vset(att_r, 15, mk(1.0f, 1.0f, 1.0f));
         } else if (depth == 0) {
           // REF: the step kernel draws the per-sample lens offset and time from its own copy of the
-          // pristine slot-0 state instead of cam_tab (measured faster here: the table read would sit
-          // in the shading phase's dependent chain)
+          // pristine slot-0 state instead of cam_tab: the mesh variants only.  (The sphere variants take the
+          // branch above: there the table read, issued early, measured 3.3 % faster than the copy, DESIGN.md
+          // 3.1j.)
           if (fresh && !per_pixel) {
-            if constexpr (PLAIN) {  // (a plain launch sets fresh with s = 0 only)
-              // The six words are needed once per item: they are read from the kernel-argument segment here,
-              // through a pointer the compiler cannot see through, instead of being held across the loop
-              // (<25730>: 75 spilled SGPRs against 80).  With the general body's copy loop as the only writer
-              // of cam, the plain kernel kept a 20-byte private segment that no instruction touches
-              // (that build is faster, and why it is not the product).
-              const RT_RO RenderParams* kp = (const RT_RO RenderParams*)__builtin_amdgcn_kernarg_segment_ptr();
-              asm volatile("" : "+s"(kp));
-              cam.d = kp->cam_state[0];
-              for (int k = 0; k < 5; ++k) cam.v[k] = kp->cam_state[1 + k];
-            } else if (s == 0) {
+            if (s == 0) {
               cam.d = P.cam_state[0];
               for (int k = 0; k < 5; ++k) cam.v[k] = P.cam_state[1 + k];
             } else {  // a split sample: the camera state at its start
