@@ -341,6 +341,41 @@ int32_t rt_last_render_schedule(const rt_ctx* ctx);
  * lists it as "general::render_step_kernel<25730>", and rt_last_render_kernel reports the same stem for
  * both. */
 int32_t rt_last_render_body(const rt_ctx* ctx);
+
+/* Debug view of the item schedule: what the context holds after the last rt_render.  Read
+ * only: neither call changes what a later launch does, and rt_render does no work for them (the fields
+ * below are host values it has anyway).  rt_render_tiles leaves everything here as it was. */
+typedef struct rt_schedule_info {
+  int64_t items;        /* items of the configuration whose counts RT_SCHED_ITEM_COST holds (0: none) */
+  int64_t n_long;       /* positions of the raised-priority prefix of RT_SCHED_PERM */
+  int64_t n_split;      /* positions of RT_SCHED_PERM whose samples are split */
+  int64_t rest_n;       /* unsplit positions (items - n_split) the claim order was sized for, -1: none */
+  int64_t pitems;       /* probe grid of the last probe launch: prow * pw points (0: no probe launch yet) */
+  int64_t spread_waves; /* waves of the last probe launch's render kernel */
+  int32_t split_state;  /* -1 nothing to split, 0 the next launch records, 1 recorded */
+  int32_t order_ok;     /* RT_SCHED_ORDER is built */
+  int32_t perm_kind;    /* what RT_SCHED_PERM holds: 0 nothing, 1 a measured schedule, 2 a probe's */
+  int32_t shift;        /* cost buckets of 2^shift segments in that schedule (-1: none) */
+  int32_t spp;          /* samples per item of that schedule's configuration */
+  int32_t ps, prow, pw; /* probe grid step, rows and columns */
+  int32_t spread_ran;   /* the last probe schedule's head was spread (spread_head_kernel ran) */
+  int32_t spread_top;   /* ... with this many strided positions per chunk of 64 (options.spread_first) */
+  int32_t perm_key_valid;    /* a later launch of the same configuration would claim through RT_SCHED_PERM */
+  int32_t pending_key_valid; /* ... would build its schedule from RT_SCHED_ITEM_COST */
+} rt_schedule_info;
+int rt_schedule_get_info(const rt_ctx* ctx, rt_schedule_info* info);
+/* Copies one device array of the schedule to the host after waiting for the context's stream.  which: */
+#define RT_SCHED_ITEM_COST 0    /* uint16[items]: segments of every item in the measuring launch       */
+#define RT_SCHED_PERM 1         /* uint32[items]: the claim order of the items                          */
+#define RT_SCHED_PROBE_RAW 2    /* uint16[pitems]: the probe launch's segment counts                    */
+#define RT_SCHED_PROBE_SMOOTH 3 /* uint16[pitems]: their neighbourhood means in 1/16 segment           */
+#define RT_SCHED_SPLIT_LEN 4    /* uint8[n_split * spp]: recorded segments of every split sample (<=255),
+                                   computed into a temporary from the recorded sample starts            */
+#define RT_SCHED_ORDER 5        /* uint32[n_split * spp + rest_n]: claim order of a split replay        */
+/* *need (may be NULL) receives the array's size in bytes, as rt_accum_save reports its blob's: out = NULL
+ * with cap_bytes = 0 asks for the size; a smaller cap_bytes is RT_ERR_ARG with nothing copied. RT_ERR_STATE when the array does not exist (nothing
+ * measured, no probe launch, nothing recorded, order not built); RT_ERR_ARG for another `which`. */
+int rt_schedule_read(rt_ctx* ctx, int32_t which, void* out, size_t cap_bytes, size_t* need);
 /* Audit log of the last RT_FLAG_AUDIT render: 16 floats per disagreeing BVH query (ray o[3] d[3]
  * time, tmin, tmax, culled t, culled prim (int bits), exact t, exact prim, culled rank, 0, 0).
  * Copies up to cap entries into out (may be NULL); returns the total number of disagreements. */

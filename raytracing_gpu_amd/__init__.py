@@ -49,6 +49,9 @@ RT_FLAG_FRESH = 256
 RT_SCHED_PREVIOUS = 1
 RT_SCHED_SPLIT_REPLAY = 2
 RT_SCHED_PROBE = 4
+# rt_schedule_read's arrays and their element types
+RT_SCHED_ITEM_COST, RT_SCHED_PERM, RT_SCHED_PROBE_RAW, RT_SCHED_PROBE_SMOOTH, RT_SCHED_SPLIT_LEN, RT_SCHED_ORDER = range(6)
+SCHED_DTYPES = ("<u2", "<u4", "<u2", "<u2", "u1", "<u4")
 
 PRIM_SPHERE, PRIM_MOVING_SPHERE, PRIM_RECT_XY, PRIM_RECT_XZ, PRIM_RECT_YZ, PRIM_TRIANGLE, PRIM_BOX = range(7)
 OBJ_PRIM, OBJ_LIST, OBJ_BVH, OBJ_XFORM, OBJ_MEDIUM = range(5)
@@ -130,6 +133,17 @@ DEFAULT_OPTIONS: dict = {}
 class rt_counters(ctypes.Structure):
     _fields_ = [("segments", c_uint64), ("node_tests", c_uint64), ("prim_tests", c_uint64),
                 ("samples", c_uint64), ("fallbacks", c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class rt_schedule_info(ctypes.Structure):
+    """include/rt_hip.h rt_schedule_info: the item schedule a context holds after its last render."""
+    _fields_ = [("items", c_int64), ("n_long", c_int64), ("n_split", c_int64), ("rest_n", c_int64), ("pitems", c_int64),
+                ("spread_waves", c_int64), ("split_state", c_int32), ("order_ok", c_int32), ("perm_kind", c_int32),
+                ("shift", c_int32), ("spp", c_int32), ("ps", c_int32), ("prow", c_int32), ("pw", c_int32),
+                ("spread_ran", c_int32), ("spread_top", c_int32), ("perm_key_valid", c_int32), ("pending_key_valid", c_int32)]
 
     def as_dict(self) -> dict:
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -247,6 +261,8 @@ ABI = {
     "rt_last_render_kernel": (ctypes.c_char_p, [c_void_p]),
     "rt_last_render_schedule": (c_int32, [c_void_p]),
     "rt_last_render_body": (c_int32, [c_void_p]),
+    "rt_schedule_get_info": (c_int, [c_void_p, POINTER(rt_schedule_info)]),
+    "rt_schedule_read": (c_int, [c_void_p, c_int32, c_void_p, c_size_t, POINTER(c_size_t)]),
     "rt_audit_log": (c_int, [c_void_p, POINTER(c_float), c_int32]),
     "rt_resolve": (c_int, [c_void_p, POINTER(rt_render_args), c_void_p, c_void_p]),
     "rt_draw": (c_int, [c_void_p, POINTER(rt_render_args), POINTER(c_uint8), POINTER(rt_counters)]),
@@ -711,6 +727,21 @@ class Context:
     def last_render_body(self) -> int:
         """Body of render_step_kernel the last render launch ran: 1 plain, 0 general (and every other kernel)."""
         return int(lib().rt_last_render_body(self._c))
+
+    def schedule_info(self) -> dict:
+        """rt_schedule_get_info: the item schedule the context holds after the last render (debug view)."""
+        o = rt_schedule_info()
+        self._check(lib().rt_schedule_get_info(self._c, ctypes.byref(o)), "rt_schedule_get_info")
+        return o.as_dict()
+
+    def schedule_read(self, which: int) -> np.ndarray:
+        """rt_schedule_read: one device array of the schedule (RT_SCHED_ITEM_COST ... RT_SCHED_ORDER) as a
+        numpy array of its element type; RtError (RT_ERR_STATE) when the context holds no such array."""
+        need = c_size_t(0)
+        self._check(lib().rt_schedule_read(self._c, which, None, 0, ctypes.byref(need)), "rt_schedule_read")
+        out = np.zeros(need.value, np.uint8)
+        self._check(lib().rt_schedule_read(self._c, which, out.ctypes.data, out.size, ctypes.byref(need)), "rt_schedule_read")
+        return out.view(SCHED_DTYPES[which])
 
     def audit_log(self, cap: int = 4096) -> tuple[int, np.ndarray]:
         """(number of disagreements, [min(n, cap), 16] float32 entries) of the last audit render."""

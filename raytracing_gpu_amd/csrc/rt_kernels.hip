@@ -2805,6 +2805,17 @@ struct rt_ctx : StreamOwner {
   Key<kKey> pending_key;  // measured, schedule not built yet
   unsigned long long pending_segs = 0;
   unsigned long long n_long = 0;
+  // What rt_schedule_get_info / rt_schedule_read report beyond the state here: host values the launches
+  // have anyway, stored as they pass (no launch, copy or wait is added for them).
+  struct SchedView {
+    long long cost_items = 0;  // item_cost holds the counts of this many items (0: nothing measured)
+    int perm_kind = 0;         // perm holds: 0 nothing, 1 build_schedule's order, 2 probe_schedule's
+    long long perm_items = 0;
+    int shift = -1, spp = 0;   // of the schedule in perm
+    int ps = 0, prow = 0, pw = 0;  // grid of the last probe launch (probe_cost: raw, then smoothed)
+    long long pitems = 0, waves = 0;
+    int spread_ran = 0, spread_top = 0;
+  } sv;
   // Split samples of the longest items (render_step_kernel; see rt_render): n_split perm positions,
   // split_state 0 = record on the next launch of perm_key, 1 = recorded for split_seed.
   unsigned long long n_split = 0;
@@ -3027,6 +3038,7 @@ void drop_schedule(rt_ctx* c) {
   c->split_state = -1;
   c->n_split = 0;
   c->order_ok = false;
+  c->sv.perm_kind = 0;
 }
 uint8_t* sort_keys(rt_ctx* c, long long n) {
   const long long tiles = (n + kOrderTile - 1) / kOrderTile;
@@ -3079,7 +3091,7 @@ __global__ __launch_bounds__(kBlock) void probe_smooth_kernel(const uint16_t* __
       ++n;
     }
   }
-  out[k] = (uint16_t)((16 * sum + n / 2) / n);
+  out[k] = (uint16_t)min(65535u, (16 * sum + n / 2) / n);  // a mean above 4095 segments saturates (it wrapped)
 }
 
 // Sort key of every item from the probe: the smoothed probe count (1/16 segment) of its grid point (sample
@@ -3161,6 +3173,10 @@ int build_schedule(rt_ctx* c, long long items, int spp, unsigned long long segs,
   long long nl = 0;  // whole buckets from the top while they fit in `want`
   for (int v = 255; v >= 0 && nl + hist[(size_t)v] <= want; --v) nl += hist[(size_t)v];
   c->n_long = (unsigned long long)nl;
+  c->sv.perm_kind = 1;
+  c->sv.perm_items = items;
+  c->sv.shift = shift;
+  c->sv.spp = spp;
   // Items that can decide when a launch ends have their samples split on later launches: the
   // items at or above a threshold set by the share's size (below).  They are the first positions
   // of perm (cost buckets descending).  (Round 2, samples still claimed in item order: C2's N = 8
@@ -3246,6 +3262,13 @@ int probe_schedule(rt_ctx* c, long long items, int spp, int width, int fbc, int 
   HIPCHK(c, hipGetLastError());
   if (int rc = sort_scatter(c, items, c->order_tab.get(), c->perm.get())) return rc;
   c->n_long = (unsigned long long)((double)items * c->opt.long_pct / 100.0);
+  c->sv.perm_kind = 2;
+  c->sv.perm_items = items;
+  c->sv.shift = shift;
+  c->sv.spp = spp;
+  c->sv.waves = waves;
+  c->sv.spread_top = spread_top;
+  c->sv.spread_ran = 0;
   // Spread head (spread_top > 0, options.spread_first): longest first, the first claims would hand the
   // estimated-longest items 64 to a wave to the waves that claim first (one workgroup's); strided, every
   // wave starts with spread_top of the head's first spread_top * waves items
@@ -3257,6 +3280,7 @@ int probe_schedule(rt_ctx* c, long long items, int spp, int width, int fbc, int 
     spread_head_kernel<<<(unsigned)std::min<long long>(4096, (n + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
         c->spread_tmp.get(), c->perm.get(), (unsigned long long)waves, (unsigned)sf);
     HIPCHK(c, hipGetLastError());
+    c->sv.spread_ran = 1;
   }
   return RT_OK;
 }
@@ -3622,6 +3646,8 @@ int schedule_state(rt_ctx* c, Launch& L) {
   if (moved_cost || moved_perm) {  // what was measured or ordered is gone
     c->perm_key.invalidate();
     c->pending_key.invalidate();
+    c->sv.cost_items = 0;
+    c->sv.perm_kind = 0;
   }
   return rc;
 }
@@ -3897,7 +3923,9 @@ int probe_grid(rt_ctx* c, Launch& L, const KernelChoice& K) {
   L.pw = (a->width + ps - 1) / std::max(1, ps);
   L.pitems = (long long)L.prow * L.pw;
   // raw counts, then the smoothed grid
-  return L.probe ? reserve(c, c->probe_cost, 2 * L.pitems, "probe counts") : RT_OK;
+  if (!L.probe) return RT_OK;
+  c->sv.pitems = 0;  // until the launch has filled the grid
+  return reserve(c, c->probe_cost, 2 * L.pitems, "probe counts");
 }
 // The probe launch and the schedule built from it, inside the timed region: P.perm, P.n_long.
 int probe_launch(rt_ctx* c, const Launch& L, const KernelChoice& K, RenderParams& P) {
@@ -3933,6 +3961,10 @@ int probe_launch(rt_ctx* c, const Launch& L, const KernelChoice& K, RenderParams
       c->probe_cost.get(), c->probe_cost.get() + L.pitems, L.prow, L.pw);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemsetAsync(c->work.get(), 0, 8 * sizeof(unsigned long long), c->stream));
+  c->sv.ps = L.ps;
+  c->sv.prow = L.prow;
+  c->sv.pw = L.pw;
+  c->sv.pitems = L.pitems;
   // The probe's schedule overwrites the context's one (perm, long prefix, split items): whatever
   // configuration perm_key named no longer has its schedule, so it runs cold again when it repeats
   // (A, A, probe of B, A must not claim A's items through B's perm).
@@ -3992,6 +4024,7 @@ int launch_and_record(rt_ctx* c, const Launch& L, const KernelChoice& K, RenderP
   if (L.sched && !L.have_perm) {  // the schedule is built from these counts when the configuration repeats
     c->pending_key = L.pkey;
     c->pending_segs = host_cnt[1];
+    c->sv.cost_items = L.items;
   }
   if (L.split_mode == 1) {  // sample-start states recorded for this seed
     c->split_state = 1;
@@ -4058,6 +4091,86 @@ float rt_last_kernel_ms(const rt_ctx* c) { return c ? c->last_kernel_ms : 0.0f; 
 const char* rt_last_render_kernel(const rt_ctx* c) { return c ? c->last_kernel : ""; }
 int32_t rt_last_render_schedule(const rt_ctx* c) { return c ? c->last_sched : 0; }
 int32_t rt_last_render_body(const rt_ctx* c) { return c ? c->last_body : 0; }
+
+int rt_schedule_get_info(const rt_ctx* c, rt_schedule_info* o) {
+  if (!c || !o) return RT_ERR_ARG;
+  const rt_ctx::SchedView& v = c->sv;
+  *o = rt_schedule_info{};
+  o->items = v.cost_items;
+  o->perm_kind = v.perm_kind;
+  const bool perm = v.perm_kind != 0;
+  o->n_long = perm ? (int64_t)c->n_long : 0;
+  o->n_split = perm ? (int64_t)c->n_split : 0;
+  o->rest_n = perm && v.perm_kind == 1 ? c->rest_n : -1;
+  o->split_state = perm ? c->split_state : -1;
+  o->order_ok = perm && c->order_ok ? 1 : 0;
+  o->shift = perm ? v.shift : -1;
+  o->spp = perm ? v.spp : 0;
+  o->ps = v.pitems > 0 ? v.ps : 0;
+  o->prow = v.pitems > 0 ? v.prow : 0;
+  o->pw = v.pitems > 0 ? v.pw : 0;
+  o->pitems = v.pitems;
+  o->spread_waves = v.waves;
+  o->spread_ran = v.perm_kind == 2 ? v.spread_ran : 0;
+  o->spread_top = v.spread_top;
+  const Key<rt_ctx::kKey> none;
+  o->perm_key_valid = c->perm_key != none ? 1 : 0;
+  o->pending_key_valid = c->pending_key != none ? 1 : 0;
+  return RT_OK;
+}
+
+int rt_schedule_read(rt_ctx* c, int32_t which, void* out, size_t cap, size_t* need) {
+  if (!c) return RT_ERR_ARG;
+  const rt_ctx::SchedView& v = c->sv;
+  const void* src = nullptr;
+  size_t bytes = 0;
+  const bool split = v.perm_kind == 1 && c->n_split > 0 && c->split_state == 1;
+  const size_t nsub = split ? (size_t)c->n_split * (size_t)v.spp : 0;
+  switch (which) {
+    case RT_SCHED_ITEM_COST:
+      if (v.cost_items > 0 && (size_t)v.cost_items <= c->item_cost.size()) src = c->item_cost.get(), bytes = (size_t)v.cost_items * 2;
+      break;
+    case RT_SCHED_PERM:
+      if (v.perm_kind != 0 && (size_t)v.perm_items <= c->perm.size()) src = c->perm.get(), bytes = (size_t)v.perm_items * 4;
+      break;
+    case RT_SCHED_PROBE_RAW:
+    case RT_SCHED_PROBE_SMOOTH:
+      if (v.pitems > 0 && 2 * (size_t)v.pitems <= c->probe_cost.size()) {
+        src = c->probe_cost.get() + (which == RT_SCHED_PROBE_SMOOTH ? v.pitems : 0);
+        bytes = (size_t)v.pitems * 2;
+      }
+      break;
+    case RT_SCHED_SPLIT_LEN:
+      if (split && 2 * nsub <= c->ckpt.size()) bytes = nsub;  // computed below
+      break;
+    case RT_SCHED_ORDER:
+      if (split && c->order_ok && c->rest_n >= 0 && nsub + (size_t)c->rest_n <= c->order.size())
+        src = c->order.get(), bytes = (nsub + (size_t)c->rest_n) * 4;
+      break;
+    default:
+      return fail(c, RT_ERR_ARG, "rt_schedule_read: unknown array");
+  }
+  if (bytes == 0) return fail(c, RT_ERR_STATE, "rt_schedule_read: the context holds no such array");
+  if (need) *need = bytes;
+  if (!out && cap == 0) return RT_OK;  // size query
+  if (!out || cap < bytes) return fail(c, RT_ERR_ARG, "rt_schedule_read: buffer too small");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (which == RT_SCHED_SPLIT_LEN) {  // into a temporary: the sort scratch and its tables stay as they are
+    uint8_t* tmp = nullptr;
+    HIPCHK(c, hipMalloc(&tmp, bytes));
+    split_len_kernel<<<(unsigned)((nsub + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(c->ckpt.get(), (unsigned long long)nsub,
+                                                                                        v.spp, tmp);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(tmp);
+    HIPCHK(c, e);
+    return RT_OK;
+  }
+  HIPCHK(c, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
 
 int rt_read_states(rt_ctx* c, int64_t first, int64_t count, uint32_t* out) {
   if (!c || !out || first < 0 || count < 0) return fail(c, RT_ERR_ARG, "bad read_states args");

@@ -98,10 +98,11 @@ def oracle_render(oracle, name: str, cam: int = REF) -> Result:
 
 
 def source_constants() -> dict:
-    """kLdsBudget, kStackDepth and kPlanePairs as rt_kernels.hip defines them."""
+    """kLdsBudget, kStackDepth and kPlanePairs as rt_kernels.hip defines them, and the schedule's kOrderTile and
+    kProbeRadius (tests/sched_ref.py)."""
     src = open(os.path.join(os.path.dirname(rt.__file__), "csrc", "rt_kernels.hip")).read()
     out = {}
-    for k in ("kLdsBudget", "kStackDepth", "kPlanePairs"):
+    for k in ("kLdsBudget", "kStackDepth", "kPlanePairs", "kOrderTile", "kProbeRadius"):
         expr = re.search(r"constexpr int %s = ([0-9* ]+);" % k, src).group(1)
         out[k] = math.prod(int(x) for x in expr.split("*"))
     return out

@@ -242,10 +242,17 @@ def test_spread_head_bit_exact(rtlib, gpu_ctx, ctx_opts, oracle, scene, spread):
         pa, oa = dict(images=[img], meshes=[m]), dict(images=[img], meshes=[(m.tris, True, 0)])
     ctx_opts(spread_first=spread)
     gpu_ctx.upload(rtlib.Scene.builtin(scene, **pa))
+    # the waves of this scene's kernel on this device, from a small probe-scheduled launch: taller where 640x360
+    # would have fewer than 64 items per wave (the spread would not run and the test would pass without it)
+    _launch(rtlib, gpu_ctx, 64, 36, spp, nfb, REF, fresh=True)
+    assert gpu_ctx.last_render_schedule() == rtlib.RT_SCHED_PROBE
+    H = max(H, -(-64 * gpu_ctx.schedule_info()["spread_waves"] // (nfb * W)))
     base, _, bcnt, s0 = _launch(rtlib, gpu_ctx, W, H, spp, nfb, REF, schedule=False)
     assert s0 == 0
     got, rows, cnt, sched = _launch(rtlib, gpu_ctx, W, H, spp, nfb, REF, fresh=True)
     assert sched == rtlib.RT_SCHED_PROBE
+    info = gpu_ctx.schedule_info()  # the spread ran (items >= 64 x the launch's waves on this device), as asked
+    assert info["spread_ran"] == 1 and info["spread_top"] == spread and nfb * W * H >= 64 * info["spread_waves"] > 0, info
     assert cnt["segments"] == bcnt["segments"] and cnt["samples"] == nfb * W * H * spp
     assert np.array_equal(_bits(got), _bits(base)), f"{scene} spread {spread}"
     sub = (5, 41)
