@@ -376,6 +376,33 @@ int rt_schedule_get_info(const rt_ctx* ctx, rt_schedule_info* info);
  * with cap_bytes = 0 asks for the size; a smaller cap_bytes is RT_ERR_ARG with nothing copied. RT_ERR_STATE when the array does not exist (nothing
  * measured, no probe launch, nothing recorded, order not built); RT_ERR_ARG for another `which`. */
 int rt_schedule_read(rt_ctx* ctx, int32_t which, void* out, size_t cap_bytes, size_t* need);
+
+/* Debug view of the camera-ray culling tables: the per-tile candidate lists (world = one
+ * BVH, the stepwise kernel) or top-level entry masks (list worlds) the context holds, and the bounding
+ * spheres they were built from.  Read only, as the schedule view above: rt_render and rt_render_tiles only
+ * store host values they have anyway. */
+typedef struct rt_camera_tiles_info {
+  int32_t kind;       /* what the tile buffer holds for the uploaded scene: 0 nothing valid, 1 lists, 2 masks */
+  int32_t width, height;     /* image size the table was built for (0 when kind = 0) */
+  int32_t tiles_x, tiles_y;  /* tiles of (1 << tile_shift)^2 pixels, the last column / row partial */
+  int32_t cap;        /* pairs per tile list (a fuller tile has count -1 and traverses the tree) */
+  int32_t tile_shift;
+  int32_t n;          /* bounding spheres of the uploaded scene (RT_CTILES_SPHERES) */
+  int32_t n_kind;     /* ... of: 0 none, 1 the world BVH's primitives, 2 the world list's entries */
+  int32_t last_used;  /* what the last rt_render / rt_render_tiles launch passed to its kernel: 0 nothing,
+                         1 lists, 2 masks */
+} rt_camera_tiles_info;
+int rt_camera_tiles_get_info(const rt_ctx* ctx, rt_camera_tiles_info* info);
+/* Copies one array to the host after waiting for the context's stream.  which: */
+#define RT_CTILES_COUNT 0   /* int32[tiles]: pairs of every tile's list, -1 = overflowed (lists)            */
+#define RT_CTILES_ENTRIES 1 /* int32[tiles * cap * 2]: (primitive id, float bits of `nearest`) pairs, ascending
+                               by `nearest`; only the first count pairs of a tile are defined (lists)      */
+#define RT_CTILES_MASK 2    /* uint32[tiles]: bit w set = a camera ray of the tile may hit entry w (masks)  */
+#define RT_CTILES_SPHERES 3 /* float[4 * n]: centre and radius of every bounding sphere                     */
+#define RT_CTILES_IDS 4     /* int32[n]: the primitive every sphere stands for (n_kind = 1)                 */
+/* Sizes and errors as rt_schedule_read: RT_ERR_STATE when the array does not exist (no table of that kind,
+ * no spheres), RT_ERR_ARG for another `which` or a buffer that is too small. */
+int rt_camera_tiles_read(rt_ctx* ctx, int32_t which, void* out, size_t cap_bytes, size_t* need);
 /* Audit log of the last RT_FLAG_AUDIT render: 16 floats per disagreeing BVH query (ray o[3] d[3]
  * time, tmin, tmax, culled t, culled prim (int bits), exact t, exact prim, culled rank, 0, 0).
  * Copies up to cap entries into out (may be NULL); returns the total number of disagreements. */

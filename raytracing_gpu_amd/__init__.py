@@ -52,6 +52,9 @@ RT_SCHED_PROBE = 4
 # rt_schedule_read's arrays and their element types
 RT_SCHED_ITEM_COST, RT_SCHED_PERM, RT_SCHED_PROBE_RAW, RT_SCHED_PROBE_SMOOTH, RT_SCHED_SPLIT_LEN, RT_SCHED_ORDER = range(6)
 SCHED_DTYPES = ("<u2", "<u4", "<u2", "<u2", "u1", "<u4")
+# rt_camera_tiles_read's arrays and their element types
+RT_CTILES_COUNT, RT_CTILES_ENTRIES, RT_CTILES_MASK, RT_CTILES_SPHERES, RT_CTILES_IDS = range(5)
+CTILES_DTYPES = ("<i4", "<i4", "<u4", "<f4", "<i4")
 
 PRIM_SPHERE, PRIM_MOVING_SPHERE, PRIM_RECT_XY, PRIM_RECT_XZ, PRIM_RECT_YZ, PRIM_TRIANGLE, PRIM_BOX = range(7)
 OBJ_PRIM, OBJ_LIST, OBJ_BVH, OBJ_XFORM, OBJ_MEDIUM = range(5)
@@ -144,6 +147,15 @@ class rt_schedule_info(ctypes.Structure):
                 ("spread_waves", c_int64), ("split_state", c_int32), ("order_ok", c_int32), ("perm_kind", c_int32),
                 ("shift", c_int32), ("spp", c_int32), ("ps", c_int32), ("prow", c_int32), ("pw", c_int32),
                 ("spread_ran", c_int32), ("spread_top", c_int32), ("perm_key_valid", c_int32), ("pending_key_valid", c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class rt_camera_tiles_info(ctypes.Structure):
+    """include/rt_hip.h rt_camera_tiles_info: the camera-ray culling table a context holds."""
+    _fields_ = [(k, c_int32) for k in ("kind", "width", "height", "tiles_x", "tiles_y", "cap", "tile_shift", "n", "n_kind",
+                                       "last_used")]
 
     def as_dict(self) -> dict:
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -263,6 +275,8 @@ ABI = {
     "rt_last_render_body": (c_int32, [c_void_p]),
     "rt_schedule_get_info": (c_int, [c_void_p, POINTER(rt_schedule_info)]),
     "rt_schedule_read": (c_int, [c_void_p, c_int32, c_void_p, c_size_t, POINTER(c_size_t)]),
+    "rt_camera_tiles_get_info": (c_int, [c_void_p, POINTER(rt_camera_tiles_info)]),
+    "rt_camera_tiles_read": (c_int, [c_void_p, c_int32, c_void_p, c_size_t, POINTER(c_size_t)]),
     "rt_audit_log": (c_int, [c_void_p, POINTER(c_float), c_int32]),
     "rt_resolve": (c_int, [c_void_p, POINTER(rt_render_args), c_void_p, c_void_p]),
     "rt_draw": (c_int, [c_void_p, POINTER(rt_render_args), POINTER(c_uint8), POINTER(rt_counters)]),
@@ -742,6 +756,23 @@ class Context:
         out = np.zeros(need.value, np.uint8)
         self._check(lib().rt_schedule_read(self._c, which, out.ctypes.data, out.size, ctypes.byref(need)), "rt_schedule_read")
         return out.view(SCHED_DTYPES[which])
+
+    def camera_tiles_info(self) -> dict:
+        """rt_camera_tiles_get_info: the camera-ray culling table the context holds and what the last render
+        launch used of it (debug view)."""
+        o = rt_camera_tiles_info()
+        self._check(lib().rt_camera_tiles_get_info(self._c, ctypes.byref(o)), "rt_camera_tiles_get_info")
+        return o.as_dict()
+
+    def camera_tiles_read(self, which: int) -> np.ndarray:
+        """rt_camera_tiles_read: one array of the table (RT_CTILES_COUNT ... RT_CTILES_IDS) as a flat numpy array
+        of its element type; RtError (RT_ERR_STATE) when the context holds no such array."""
+        need = c_size_t(0)
+        self._check(lib().rt_camera_tiles_read(self._c, which, None, 0, ctypes.byref(need)), "rt_camera_tiles_read")
+        out = np.zeros(need.value, np.uint8)
+        self._check(lib().rt_camera_tiles_read(self._c, which, out.ctypes.data, out.size, ctypes.byref(need)),
+                    "rt_camera_tiles_read")
+        return out.view(CTILES_DTYPES[which])
 
     def audit_log(self, cap: int = 4096) -> tuple[int, np.ndarray]:
         """(number of disagreements, [min(n, cap), 16] float32 entries) of the last audit render."""

@@ -2851,6 +2851,7 @@ struct rt_ctx : StreamOwner {
   int last_sched = 0;  // RT_SCHED_* of the last render launch
   char last_kernel[48] = "";  // rocprof name stem of the last render launch, e.g. render_step_kernel<25730>
   int last_body = 0;  // ... and the body it ran: 1 = render_step_kernel's plain body (RT_STEP_PLAIN), 0 = the general one
+  int last_tiles = 0;  // ... and the camera tile table it was passed: 0 none, 1 tile_cnt / tile_ent, 2 tile_mask
   DevBuf<float> dbg;  // audit log: [0] = count, then 16 floats per entry
   // Camera-ray candidate lists (world = one BVH): bounding spheres of the world BVH's primitives
   // over the shutter (scene buffers) and the per-tile lists of the last (scene, W, H).
@@ -4009,6 +4010,7 @@ int launch_and_record(rt_ctx* c, const Launch& L, const KernelChoice& K, RenderP
   snprintf(c->last_kernel, sizeof(c->last_kernel), "%s<%d>",
            (K.mask & F_STEP) != 0 ? "render_step_kernel" : "render_kernel", K.mask);
   c->last_body = plain ? 1 : 0;
+  c->last_tiles = P.tile_cnt ? 1 : P.tile_mask ? 2 : 0;
   unsigned long long host_cnt[8];
   HIPCHK(c, hipMemcpyAsync(host_cnt, c->work.get(), sizeof(host_cnt), hipMemcpyDeviceToHost, c->stream));
   std::vector<unsigned long long> cost(L.measure_rows ? (size_t)a->height : 0);
@@ -4167,6 +4169,68 @@ int rt_schedule_read(rt_ctx* c, int32_t which, void* out, size_t cap, size_t* ne
     HIPCHK(c, e);
     return RT_OK;
   }
+  HIPCHK(c, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+// What the tile buffer holds for the uploaded scene, from tiles_key (camera_culling): 0 nothing, 1 lists, 2 masks.
+static int camera_tiles_kind(const rt_ctx* c, int* W, int* H) {
+  const auto& k = c->tiles_key.v;
+  if (!c->have_scene || k[0] != c->scene_gen || k[1] <= 0 || k[2] == 0) return 0;
+  *W = (int)k[1];
+  *H = (int)(k[2] > 0 ? k[2] : -1 - k[2]);
+  return k[2] > 0 ? 1 : 2;
+}
+
+int rt_camera_tiles_get_info(const rt_ctx* c, rt_camera_tiles_info* o) {
+  if (!c || !o) return RT_ERR_ARG;
+  *o = rt_camera_tiles_info{};
+  int W = 0, H = 0;
+  o->kind = camera_tiles_kind(c, &W, &H);
+  o->width = W, o->height = H;
+  o->tiles_x = (W + (1 << kTileShift) - 1) >> kTileShift;
+  o->tiles_y = (H + (1 << kTileShift) - 1) >> kTileShift;
+  o->cap = kTileCap;
+  o->tile_shift = kTileShift;
+  const bool sph = c->have_scene && c->bin_sph && c->bin_n != 0;
+  o->n = sph ? abs(c->bin_n) : 0;
+  o->n_kind = !sph ? 0 : c->bin_n > 0 ? 1 : 2;
+  o->last_used = c->last_tiles;
+  return RT_OK;
+}
+
+int rt_camera_tiles_read(rt_ctx* c, int32_t which, void* out, size_t cap, size_t* need) {
+  if (!c) return RT_ERR_ARG;
+  rt_camera_tiles_info v;
+  rt_camera_tiles_get_info(c, &v);
+  const size_t nt = (size_t)v.tiles_x * (size_t)v.tiles_y, ntp = (nt + 3) & ~(size_t)3;  // as camera_culling lays them out
+  const void* src = nullptr;
+  size_t bytes = 0;
+  switch (which) {
+    case RT_CTILES_COUNT:
+      if (v.kind == 1 && ntp + nt * kTileCap * 2 <= c->tiles.size()) src = c->tiles.get(), bytes = nt * 4;
+      break;
+    case RT_CTILES_ENTRIES:
+      if (v.kind == 1 && ntp + nt * kTileCap * 2 <= c->tiles.size()) src = c->tiles.get() + ntp, bytes = nt * kTileCap * 2 * 4;
+      break;
+    case RT_CTILES_MASK:
+      if (v.kind == 2 && nt <= c->tiles.size()) src = c->tiles.get(), bytes = nt * 4;
+      break;
+    case RT_CTILES_SPHERES:
+      if (v.n > 0) src = c->bin_sph, bytes = (size_t)v.n * 16;
+      break;
+    case RT_CTILES_IDS:
+      if (v.n > 0 && v.n_kind == 1 && c->bin_ids) src = c->bin_ids, bytes = (size_t)v.n * 4;
+      break;
+    default:
+      return fail(c, RT_ERR_ARG, "rt_camera_tiles_read: unknown array");
+  }
+  if (bytes == 0) return fail(c, RT_ERR_STATE, "rt_camera_tiles_read: the context holds no such array");
+  if (need) *need = bytes;
+  if (!out && cap == 0) return RT_OK;  // size query
+  if (!out || cap < bytes) return fail(c, RT_ERR_ARG, "rt_camera_tiles_read: buffer too small");
+  HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RT_OK;

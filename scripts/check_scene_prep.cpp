@@ -185,6 +185,65 @@ void ref_dfs(const rt_scene_soa* s, int base, int rows, int k, int level, int& s
   ref_dfs(s, base, rows, 2 * k + 2, level + 1, slot, f);
 }
 
+// The camera-bin bounding spheres (P.bin_sph), in double.  A sphere contains a box when it contains its corners.
+struct Pt {
+  double x[3];
+};
+void corners(const rth::Box& b, std::vector<Pt>& out) {
+  for (int q = 0; q < 8; ++q)
+    out.push_back(Pt{{(q & 1) ? b.hi[0] : b.lo[0], (q & 2) ? b.hi[1] : b.lo[1], (q & 4) ? b.hi[2] : b.lo[2]}});
+}
+bool sphere_contains(const rtprep::Float4& sp, const std::vector<Pt>& pts) {
+  if (sp.w == INFINITY) return true;
+  for (const Pt& p : pts) {
+    const double d[3] = {p.x[0] - sp.x, p.x[1] - sp.y, p.x[2] - sp.z};
+    if (!(std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) <= (double)sp.w)) return false;
+  }
+  return true;
+}
+// Corner points, in world space, of what object oi holds over the shutter: a primitive's box, the boxes of a
+// list's or a BVH's primitives, a medium's boundary, and for an instance the eight corners of its child's box
+// through translate(rotate_y(.)) (hittable.h: world = (c x + s z, y, -s x + c z) + offset).  false: no box.
+bool object_corners(const rt_scene_soa* s, int oi, std::vector<Pt>& out, int depth = 0) {
+  if (oi < 0 || oi >= s->n_objects || depth > 8) return false;
+  const rt_object& o = s->objects[oi];
+  switch (o.kind) {
+    case RT_OBJ_PRIM:
+      corners(geom_box(s, o.a), out);
+      return true;
+    case RT_OBJ_LIST:
+      for (int k = 0; k < o.b; ++k) corners(geom_box(s, o.a + k), out);
+      return o.b > 0;
+    case RT_OBJ_BVH: {
+      int slot = 0, n = 0;
+      ref_dfs(s, o.a, o.b, 0, 0, slot, [&](int id, int) {
+        corners(geom_box(s, id), out);
+        ++n;
+      });
+      return n > 0;
+    }
+    case RT_OBJ_MEDIUM:
+      return object_corners(s, o.a, out, depth + 1);
+    case RT_OBJ_XFORM: {
+      std::vector<Pt> child;
+      if (!object_corners(s, o.a, child, depth + 1)) return false;
+      double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+      for (const Pt& p : child)
+        for (int a = 0; a < 3; ++a) lo[a] = std::fmin(lo[a], p.x[a]), hi[a] = std::fmax(hi[a], p.x[a]);
+      const double sn = (o.b & 2) ? o.f[3] : 0.0, cs = (o.b & 2) ? o.f[4] : 1.0;
+      for (int q = 0; q < 8; ++q) {
+        const double x = (q & 1) ? hi[0] : lo[0], y = (q & 2) ? hi[1] : lo[1], z = (q & 4) ? hi[2] : lo[2];
+        Pt w{{cs * x + sn * z, y, -sn * x + cs * z}};
+        if (o.b & 1)
+          for (int a = 0; a < 3; ++a) w.x[a] += o.f[a];
+        out.push_back(w);
+      }
+      return true;
+    }
+  }
+  return false;
+}
+
 bool check_run(const rt_scene_soa* s, const rtprep::Options& opt, const rtprep::Prepared& P) {
   CHECK((int)P.prims.size() == s->n_prims && (int)P.objects.size() == s->n_objects);
   // the first node of each tree built here, in the order they were appended: each ends where the next begins
@@ -291,6 +350,36 @@ bool check_run(const rt_scene_soa* s, const rtprep::Options& opt, const rtprep::
     std::vector<int> seen((size_t)s->n_world, 0);
     CHECK((int)P.worder.size() == s->n_world);
     for (int32_t w : P.worder) CHECK(w >= 0 && w < s->n_world && !seen[(size_t)w]++);
+  }
+
+  // Camera-bin bounding spheres: a sphere contains what it stands for (the camera tile lists and entry masks
+  // drop whatever lies outside a tile's frustum by more than its sphere's radius).
+  if (P.world_bvh) {  // one per leaf of the world BVH, in the reference's depth-first order
+    const rt_object& o = s->objects[s->world[0]];
+    std::vector<int> members;
+    int slot = 0;
+    ref_dfs(s, o.a, o.b, 0, 0, slot, [&](int id, int) { members.push_back(id); });
+    CHECK(P.bin_n == (int)members.size() && P.bin_ids.size() == members.size() && P.bin_sph.size() == members.size());
+    for (size_t q = 0; q < members.size(); ++q) {
+      CHECK(P.bin_ids[q] == members[q]);
+      const rtprep::Float4& sp = P.bin_sph[q];
+      const rth::Box b = geom_box(s, members[q]);
+      std::vector<Pt> pts;
+      corners(b, pts);
+      CHECK(sphere_contains(sp, pts));
+      // ... and is no looser than box_sphere's 1e-6 terms allow, with a tenfold margin
+      const double h[3] = {0.5 * ((double)b.hi[0] - b.lo[0]), 0.5 * ((double)b.hi[1] - b.lo[1]), 0.5 * ((double)b.hi[2] - b.lo[2])};
+      const double half_diag = std::sqrt(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
+      const double c1 = std::fabs((double)sp.x) + std::fabs((double)sp.y) + std::fabs((double)sp.z);
+      CHECK((double)sp.w - half_diag <= 1e-5 * ((double)sp.w + c1));
+    }
+  } else {  // one per top-level entry (the first 32): around the entry's box, or unbounded
+    CHECK(P.bin_ids.empty() && P.bin_n == -(int)P.bin_sph.size() && (int)P.bin_sph.size() == (s->n_world < 32 ? s->n_world : 32));
+    for (size_t w = 0; w < P.bin_sph.size(); ++w) {
+      std::vector<Pt> pts;
+      if (object_corners(s, s->world[w], pts)) CHECK(sphere_contains(P.bin_sph[w], pts));
+      else CHECK(P.bin_sph[w].w == INFINITY);
+    }
   }
 
   if (P.plane_fb >= 0) {  // only the last tree of nodes, of at most kPlanePairs records

@@ -551,6 +551,8 @@ def test_camera_lists_on_and_off(rtlib, gpu_ctx, oracle, threshold, ctx_opts):
     ctx_opts(bins_min_items_per_lane=float(threshold))
     W, H, spp, nfb = 96, 54, 2, 2
     gpu, rows, cnt, _, _ = _gpu_render(rtlib, gpu_ctx, "big1", W, H, spp, 0, nfb, REF)
+    # the case ran what its name says: the launch was handed the tile lists, or nothing
+    assert gpu_ctx.camera_tiles_info()["last_used"] == (1 if threshold == "0" else 0)
     ref = oracle.RefScene("big1")
     segs = 0
     for f in range(nfb):

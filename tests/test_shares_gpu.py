@@ -114,6 +114,9 @@ def test_step_share_across_camera_list_switch(rtlib, gpu_ctx, oracle, ctx_opts, 
     rank = n - 1
     gpu_ctx.upload(rtlib.Scene.builtin("big1"))
     got, rows, _ = _share(rtlib, gpu_ctx, W, H, spp, nfb, (4, rank, n), 3, "render_step_kernel<")
+    # the lists were handed to the kernel on one side of the threshold only: N = 4 lies above 6, N = 8 below
+    lists = {None: n == 4, "0": True, "1e9": False}[threshold]
+    assert gpu_ctx.camera_tiles_info()["last_used"] == (1 if lists else 0)
     sub = (4 * rank + 2, 4 * n * 7)
     js = list(range(sub[0], H, sub[1]))
     pos = {int(j): q for q, j in enumerate(rows)}

@@ -173,6 +173,7 @@ def test_camera_tile_lists_on_and_off(rtlib, gpu_ctx, oracle, cam, bins):
     spp = 2
     gpu_ctx.upload(rtlib.Scene.builtin("big1"))
     got, rows, cnt = _launch(rtlib, gpu_ctx, W0, H0, spp, NFB0, cam, bins=bins)
+    assert gpu_ctx.camera_tiles_info()["last_used"] == (1 if bins else 0)
     assert gpu_ctx.last_render_kernel() == STEP
     assert gpu_ctx.last_render_body() == PLAIN
     _check(got, rows, cnt, W0, H0, spp, NFB0, cam)
