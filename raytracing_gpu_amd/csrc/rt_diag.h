@@ -26,10 +26,23 @@
 // 4 / 5 leaf passes entered first (a step's first pass, or the first pass of a vote) and the lanes
 // testing a leaf in them, 6 / 7 the same for the passes that follow it (a lane's second leaf),
 // 8 / 9 render_step_kernel's shading passes that enter the refill and the lanes without an item in
-// them, 10 chunks claimed from the work counter
-constexpr int kStepCounts = 11;
+// them, 10 chunks claimed from the work counter;
+// from 11 on, render_step_kernel's shading passes by pass index (0, 1 and later), ten counts each
+// (RT_STEP_PASS_LANES): 0 passes run, 1 lanes entering the heavy block (settle, hit record, scatter), 2 lanes
+// in its hit branch, 3 / 4 / 5 paths ended there by a miss / no scatter / the depth limit, 6 lanes that get
+// a camera ray, 7 / 8 of those answered by their tile's list with / without a candidate, 9 lanes ended by
+// the miss-first block (RT_STEP_MISS_FIRST)
+constexpr int kStepPass0 = 11, kStepPassStride = 10, kStepPassSlots = 2;
+constexpr int kStepCounts = kStepPass0 + kStepPassStride * kStepPassSlots;
+static_assert(kStepCounts <= 64, "one lane per count at the wave's end");
 __device__ unsigned long long rt_diag_steps[kStepCounts];
-__shared__ unsigned long long rt_diag_steps_acc[16][kStepCounts];
+// Static LDS on top of the kernels' dynamic image (kLdsBudget, 156 KB of 160): the eleven loop counts as
+// before (1 408 B) and the per-pass counts as 32-bit words per wave (1 280 B; a wave's own share of a launch
+// is far below 2^32), 2 688 B together; with the stamps' 1 408 B (RT_DIAG=3) exactly the 4 KB left.
+__shared__ unsigned long long rt_diag_steps_acc[16][kStepPass0];
+__shared__ unsigned rt_diag_pass_acc[16][kStepPassStride * kStepPassSlots];
+static_assert(sizeof(unsigned long long) * 16 * kStepPass0 + sizeof(unsigned) * 16 * kStepPassStride * kStepPassSlots +
+              sizeof(unsigned long long) * 16 * 11 <= 4096, "the diagnostic accumulators and the stamps fit beside kLdsBudget");
 __device__ __forceinline__ void rt_step_count(int k) {  // one count per wave (first active lane)
   const unsigned long long act = __ballot(1);
   if ((int)__lane_id() == __ffsll((long long)act) - 1) {
@@ -37,12 +50,29 @@ __device__ __forceinline__ void rt_step_count(int k) {  // one count per wave (f
     if (k == 0 || k == 4 || k == 6 || k == 8) rt_diag_steps_acc[threadIdx.x >> 6][k + 1] += __popcll(act);
   }
 }
+// count k of shading pass `pass` += the lanes of `mask` (a ballot of the active lanes)
+__device__ __forceinline__ void rt_step_pass_lanes(int pass, int k, unsigned long long mask) {
+  const unsigned long long act = __ballot(1);
+  const int slot = pass < kStepPassSlots ? pass : kStepPassSlots - 1;
+  if ((int)__lane_id() == __ffsll((long long)act) - 1)
+    rt_diag_pass_acc[threadIdx.x >> 6][kStepPassStride * slot + k] += (unsigned)__popcll(mask);
+}
+__device__ __forceinline__ void rt_step_count_begin() {
+  const int l = (int)__lane_id(), w = threadIdx.x >> 6;
+  if (l < kStepPass0) rt_diag_steps_acc[w][l] = 0;
+  else if (l < kStepCounts) rt_diag_pass_acc[w][l - kStepPass0] = 0;
+}
+__device__ __forceinline__ void rt_step_count_end() {
+  const int l = (int)__lane_id(), w = threadIdx.x >> 6;
+  if (l < kStepPass0) atomicAdd(&rt_diag_steps[l], rt_diag_steps_acc[w][l]);
+  else if (l < kStepCounts) atomicAdd(&rt_diag_steps[l], (unsigned long long)rt_diag_pass_acc[w][l - kStepPass0]);
+}
 #define RT_STEP_COUNT(k) rt_step_count(k)
-#define RT_STEP_COUNT_BEGIN() \
-  if (__lane_id() < kStepCounts) rt_diag_steps_acc[threadIdx.x >> 6][__lane_id()] = 0
-#define RT_STEP_COUNT_END() \
-  if (__lane_id() < kStepCounts) atomicAdd(&rt_diag_steps[__lane_id()], rt_diag_steps_acc[threadIdx.x >> 6][__lane_id()])
-#define RT_STEP_COUNT_HOST_RESET()                                   \
+#define RT_STEP_PASS_LANES(pass, k, cond) rt_step_pass_lanes(pass, k, __ballot(cond))
+#define RT_STEP_PASS_RUN(pass) rt_step_pass_lanes(pass, 0, 1ull)
+#define RT_STEP_COUNT_BEGIN() rt_step_count_begin()
+#define RT_STEP_COUNT_END() rt_step_count_end()
+#define RT_STEP_COUNT_HOST_RESET()                                  \
   do {                                                               \
     const unsigned long long z_[kStepCounts] = {};                   \
     (void)hipMemcpyToSymbol(HIP_SYMBOL(rt_diag_steps), z_, sizeof(z_)); \
@@ -55,9 +85,20 @@ __device__ __forceinline__ void rt_step_count(int k) {  // one count per wave (f
             " leaf_first=%llu leaf_first_lanes=%llu leaf_more=%llu leaf_more_lanes=%llu"                    \
             " refill_passes=%llu refill_lanes=%llu chunk_claims=%llu\n",                                    \
             var, h_[0], h_[1], h_[2], h_[3], h_[4], h_[5], h_[6], h_[7], h_[8], h_[9], h_[10]);              \
+    for (int p_ = 0; p_ < kStepPassSlots; ++p_) {                                                           \
+      const unsigned long long* q_ = h_ + kStepPass0 + kStepPassStride * p_;                                \
+      if (q_[0] != 0)                                                                                       \
+        fprintf(stderr, "RT_STEP_PASS var=%d pass=%d%s passes=%llu heavy_lanes=%llu hit_lanes=%llu end_miss=%llu"   \
+                " end_noscatter=%llu end_depth=%llu camera_lanes=%llu listed_hit=%llu listed_none=%llu"     \
+                " miss_first=%llu\n",                                                                       \
+                var, p_, p_ == kStepPassSlots - 1 ? "+" : "", q_[0], q_[1], q_[2], q_[3], q_[4], q_[5],     \
+                q_[6], q_[7], q_[8], q_[9]);                                                                \
+    }                                                                                                       \
   } while (0)
 #else
 #define RT_STEP_COUNT(k)
+#define RT_STEP_PASS_LANES(pass, k, cond)
+#define RT_STEP_PASS_RUN(pass)
 #define RT_STEP_COUNT_BEGIN()
 #define RT_STEP_COUNT_END()
 #define RT_STEP_COUNT_HOST_RESET()

@@ -1999,6 +1999,31 @@ constexpr int kShadeMinMesh = 48;  // ... for triangle-mesh variants (round 5, w
                                    // 36 / 40 / 44 / 48 / 52 / 56 / 60: 18 845 / 18 971 / 19 048 / 19 079 /
                                    // 19 021 / 18 750 / 17 986 Mrays/s; profiles/r05/shade_ab.txt)
 constexpr int kShadePasses = 2;    // render_step_kernel: shading passes per phase (1: C2 17.2 -> 20.4 ms, 3: +0.7 %)
+// The sphere variants' pass order (rt_step_body.h): a pass first ends the searches that
+// certainly missed (block A: att * bg and the sample-end bookkeeping, none of settle / finalize / scatter),
+// then refills, then sets up the camera rays (Q), and only then runs the heavy block (C) once, for bounce
+// hits and the camera rays that their tile's list answered with a hit together.  Per lane the float
+// operations, the RNG draws and their order are the parent's; only the interleaving between lanes moves.
+// -DRT_STEP_MISS_FIRST=0: the parent's order (A/B; its machine code in every kernel but the counting twin
+// <25731>, which differs by one instruction).  Not with F_CHECK, whose audit re-runs every
+// query, a miss included.
+#ifndef RT_STEP_MISS_FIRST
+#define RT_STEP_MISS_FIRST 1
+#endif
+template <int F>
+constexpr bool step_miss_first() { return RT_STEP_MISS_FIRST != 0 && step_sphere(F) && (F & F_CHECK) == 0; }
+// A search that certainly missed: no candidate, no subtree dropped on stack overflow, and no primitive entry
+// after the BVH in the world list (S.n_world: wave-uniform).  bvh_settle returns false for it at once,
+// tests nothing, counts nothing and draws nothing.
+__device__ __forceinline__ bool step_sure_miss(const DScene& S, int best_prim, bool overflow) {
+  return S.n_world == 1 && best_prim < 0 && !overflow;
+}
+// A phase of that order is ONE pass: what it leaves pending after C (listed camera misses, paths that ended
+// inside C) waits through the traversal loop.  Swept on C2 with a rule "another pass while at least m lanes
+// are pending and fewer than p passes have run" (kernel_ms, the parent's order 13.75): p = 2 with m = 1 / 8 /
+// 16 / 32: 12.11 / 11.99 / 11.97 / 11.96; p = 3 with m = 1 / 8 / 16: 12.12 / 11.94 / 11.92; p = 4, m = 16: 11.94;
+// one pass: 11.82.  With C inside the pass a second pass has little to shade: nine camera
+// rays in ten are answered with a hit and shaded at once.  So the rule and its constants are not in the tree.
 constexpr unsigned kChunk = 64;  // items a wave claims per work-counter atomic
 static_assert(kChunk >= 64, "claim_items: one claim must cover a refill of every lane of a wave");
 

@@ -4,6 +4,8 @@
 // says which body this is (RT_STEP_PLAIN there: which launches run which, and why their frame buffers are
 // the same bits).  The text is shared as text, not as a function template, so that a kernel compiles to
 // the machine code it had when the text stood in it (scripts/isa_same.py).  In scope: F, P.
+// Three blocks of a shading pass that run at more than one place are fragments of their own, for the same
+// reason: rt_step_body_heavy.h, rt_step_body_end.h, rt_step_body_query.h.
 #ifndef RT_STEP_BODY_PLAIN
 #error "rt_step_body.h is the body of render_step_kernel only"
 #endif
@@ -104,13 +106,24 @@
   // The entry is read where s is set (the sample end, the hand-out of an item), ahead of the refill; the
   // camera setup of the same pass consumes it (cam_e).
   constexpr bool TAB = step_sphere(F);
+  // The miss-first pass order of the sphere variants (step_miss_first in rt_kernels.hip): blocks A, R, Q, C
+  // below.  Lanes share no state and each runs its own float operations and RNG draws in its own order, so
+  // only the interleaving between lanes differs from the parent's order.
+  constexpr bool MF = step_miss_first<F>();
   RT_WAVE_T0();
 
   const RenderParams& P0 = P;
   for (;;) {
     // Shading passes: a camera ray answered by its tile's candidate list (mode 2 right after the
     // setup) is shaded in another pass of the same phase, so the traversal loop that follows
-    // starts with every lane traversing.
+    // starts with every lane traversing.  (The miss-first order shades it in block C of the pass that set
+    // it up; what its passes leave pending -- listed camera misses, paths that ended in C -- waits through
+    // the traversal loop.)
+    // Invariants of both orders: the traversal loop starts with no lane holding an untested leaf and `pend`
+    // is not live across the phase (the loop's flush pass tests every leaf held before it breaks, and no
+    // pass touches `pend`); item_segs and nseg grow once per segment; in split launches a lane writes its
+    // `ckpt` record at the same point of its own sequence (the camera setup of sample s > 0, the item's
+    // end) with the same `loc` and item_segs, whichever pass that point falls into.
     for (int pass = 0;; ++pass) {
       // The arguments that only the shading passes read (the frame buffer and its layout, spp, max_depth,
       // the image size, the background, the tile lists, the camera, the work counter and the item decode's
@@ -120,136 +133,35 @@
       const RenderParams& P = shade_params<F, PLAIN>(P0);
       const rt_camera& C = P.S.cam;
       RT_STEP_COUNT(2);
+      RT_STEP_PASS_RUN(pass);
       float4 cam_e = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // TAB: cam_tab[s] of a lane whose sample starts in this pass
-      // ---- shading phase: finish the ended queries (render.h:60-77)
+      // MF: cam_e holds the lane's entry.  A path that ends in block C sets s after this pass's camera
+      // setup; its entry is read at the setup of a later pass instead (rare: no scatter, the depth limit).
+      bool cam_have = false;
+      // The blocks of a pass are text fragments (rt_step_body_heavy.h, _end.h, _query.h), each written once
+      // and included where an order runs it: as lambdas they changed the machine code of the mesh and world-tree variants too.
+      // ---- shading phase
       RT_STAMP(7);  // back-to-back pair: phase 7 = the cost of one stamp per loop trip
-      RT_STAMP(5);
+      RT_STAMP(MF ? 0 : 5);
+      if constexpr (MF) {
+        // ---- A. end the certain misses (step_sure_miss: bvh_settle would return false at once and draws
+        // nothing): one segment, att * bg, the sample end.  Every other waiting lane, an overflowed or
+        // uncertain search included, is left for C.  item_segs and nseg grow once per segment: here or at
+        // the head of the heavy block, never both -- C takes !step_sure_miss() only, and a lane that A ends
+        // leaves mode 2.
+        if (mode == 2 && step_sure_miss(S, best_prim, overflow)) {
+          RT_STEP_PASS_LANES(pass, 9, true);
+          ++nseg;
+          ++item_segs;
+          const V contrib = vget(att_r, 15) * ld3(P.S.bg);
+          constexpr bool END_READS_TAB = true;
+#include "rt_step_body_end.h"
+          mode = 0;
+        }
+      } else {
       if (mode == 2) {
-        ++nseg;
-        ++item_segs;
-        bool ended = false;
-        V contrib;
-        Hit h;
-        bool hit;
-        if constexpr ((F & F_WORLD) != 0) {
-          // list world: the tree's winner, then the constant media that follow every tree entry in
-          // the list, in list order with the closest hit so far (their RNG draws depend on it);
-          // anything uncertain -- near ties, a chain the reference may reject, a ray that could
-          // make an inert medium draw -- runs the reference's sequential list exactly
-          constexpr int FM = F & ~(F_WORLD | F_STEP | F_BVH);  // media boundaries are primitives
-          int wobj = -1, wprim = -1;
-          int st = world_settle<F>(S, ray, tmin, overflow, bhi, second, best, best_prim, best_rank, wobj, wprim, nnode);
-          if (S.w_inert && !ray_sane(ray)) st = 2;
-          const bool exact = st == 2;
-          if constexpr ((F & F_STATS) != 0) nfall += exact ? 1u : 0u;
-          hit = st == 1;
-          // exact: every entry in list order (the reference's visit sets); else the media after the tree
-          for (int w = exact ? 0 : S.w_media; w < S.n_world; ++w) {
-            const int oi = ro<F>(S.world)[w];
-            const rt_object o = ro<F>(S.objects)[oi];
-            float tq;
-            int pq;
-            bool hq;
-            const float tcl = hit ? best : tmax;
-            if (o.kind == RT_OBJ_MEDIUM) {
-              hq = object_query<FM>(S, oi, ray, tmin, tcl, tq, pq, loc, nnode, nprim, nfall);
-            } else {
-              Ray rr = ray;
-              int xi = oi;
-              if constexpr ((F & F_XFORM) != 0) if (o.kind == RT_OBJ_XFORM) {
-                Ray moved;
-                rr = xform_ray(o, ray, moved);
-                xi = o.a;
-              }
-              const rt_object x = ro<F>(S.objects)[xi];
-              if ((F & F_BVH) != 0 && x.kind == RT_OBJ_BVH) {
-                hq = bvh_exact<F>(S, x.a, x.b, rr, mk(1.0f / rr.d.x, 1.0f / rr.d.y, 1.0f / rr.d.z), tmin, tcl, tq, pq,
-                                  nnode, nprim, nfall);
-              } else {
-                pq = x.a;
-                hq = prim_t<F>(S, x.a, rr, tmin, tcl, tq, nprim);
-              }
-            }
-            if (hq) {
-              hit = true;
-              best = tq;
-              wobj = oi;
-              wprim = pq;
-            }
-          }
-          if (hit) object_record<FM>(S, wobj, wprim, ray, tmin, best, h);
-        } else {
-          hit = bvh_settle<F>(S, obj.a, obj.b, ray, tmin, tmax, overflow, bhi, second, best, best_prim, best_rank,
-                              nnode, nprim, nfall);
-          // primitive objects after the BVH in the world list (C4's ground sphere): hittable_list's
-          // rule, t_max = the closest hit so far (inclusive), so a later entry wins a tie
-          for (int w = 1; w < S.n_world; ++w) {
-            const rt_object po = ro<0>(S.objects)[ro<0>(S.world)[w]];  // uniform: scalar loads
-            float tq;
-            if (prim_t_q<F>(S, load_prim_u<F>(S, po.a), ray, tmin, hit ? best : tmax, tq, nprim)) {
-              hit = true;
-              best = tq;
-              best_prim = po.a;
-            }
-          }
-          if (hit) finalize<F>(S, best_prim, ray, tmin, best, h);
-        }
-        if (!hit) {
-          contrib = vget(att_r, 15) * ld3(P.S.bg);
-          ended = true;
-        } else {
-          V a, em;
-          RT_STAMP(6);
-          bool sc;
-          if constexpr (PKS) {  // on a register copy of the parked state
-            Rng lr = loc;
-            sc = scatter<F>(S, ray, h, a, em, lr);
-            loc = lr;
-          } else {
-            sc = scatter<F>(S, ray, h, a, em, loc);
-          }
-          if (sc) {
-            vset(att_r, 15, vget(att_r, 15) * a);
-            if (++depth == P.max_depth) {
-              contrib = mk(0.0f, 0.0f, 0.0f);
-              ended = true;
-            }
-          } else {
-            contrib = vget(att_r, 15) * em;
-            ended = true;
-          }
-        }
-        RT_STAMP(0);
-        if (ended) {
-          const V col = vget(col_r, 12) + contrib;
-          vset(col_r, 12, col);
-          depth = 0;
-          ++nsamp;
-          // the item ends after sample spp - 1, a split item's sample (split_mode 2) after itself
-          // (parking variants derive it from ck: sample ck % spp)
-          if constexpr (PKS) s_end_r = (P.split_mode == 2 && ck >= 0) ? ck - (ck / P.spp) * P.spp + 1 : P.spp;
-          const bool item_ends = ++s == (PLAIN ? P.spp : s_end_r);
-          if (TAB && !per_pixel && !item_ends) cam_e = P.S.cam_tab[s];  // the next sample's, below spp
-          if (item_ends) {
-            if (SPLIT && P.split_mode == 2 && ck >= 0) {  // one sample of a split item: its sum, merged later
-              float* dst = P.contrib + 3 * (long long)ck;
-              dst[0] = col.x;
-              dst[1] = col.y;
-              dst[2] = col.z;
-            } else {
-              const V out = (1.0f / (float)P.spp) * col;
-              float* dst = P.fb + 3 * (((long long)f * P.rows + r) * P.W + i);
-              dst[0] = out.x;
-              dst[1] = out.y;
-              dst[2] = out.z;
-            }
-            if (P.row_cost && (i & 15) == 0) atomicAdd(&P.row_cost[j], (unsigned long long)item_segs);
-            if (P.item_cost) P.item_cost[item] = (uint16_t)(item_segs < 65535u ? item_segs : 65535u);
-            if (SPLIT && P.split_mode == 1 && ck >= 0) P.ckpt[2 * (long long)ck * P.spp + 1] = make_uint4(0u, 0u, item_segs, 0u);
-            item = -1;
-          }
-        }
-        mode = 0;
+#include "rt_step_body_heavy.h"
+      }
       }
       RT_STAMP(8);
       // ---- refill lanes without an item from the wave's chunk of the work counter (one atomic
@@ -315,7 +227,10 @@
               s = 0;
               if constexpr (!PLAIN) s_end_r = P.spp;
               if constexpr (!TAB) fresh = 1;
-              if (TAB && !per_pixel) cam_e = P.S.cam_tab[0];
+              if (TAB && !per_pixel) {
+                cam_e = P.S.cam_tab[0];
+                cam_have = true;
+              }
               depth = 0;
               item_segs = 0;
               col_r = mk(0, 0, 0);
@@ -372,7 +287,10 @@
             s = sa;
             if constexpr (!PKS) s_end_r = (P.split_mode == 2 && ck >= 0) ? sa + 1 : P.spp;
             if constexpr (!TAB) fresh = 1;
-            if (TAB && !per_pixel) cam_e = P.S.cam_tab[sa];  // (a split sample needs no camera state)
+            if (TAB && !per_pixel) {  // (a split sample needs no camera state)
+              cam_e = P.S.cam_tab[sa];
+              cam_have = true;
+            }
             depth = 0;
             item_segs = 0;
             vset(col_r, 12, mk(0, 0, 0));
@@ -387,7 +305,10 @@
       }
       // ---- next query: camera ray at a sample's start (render.h:105-108, camera.h:49-58)
       RT_STAMP(1);
+      // (Q of the miss-first order: there every lane that comes here starts a sample, a scattered ray's
+      // search having started in C.)
       if (item >= 0 && mode == 0) {
+        RT_STEP_PASS_LANES(pass, 6, MF || depth == 0);
         // camera ray: its tile's candidate list (count + first entries) is loaded before the ray is
         // generated, so the loads overlap the camera arithmetic
         const bool listed = (F & F_WORLD) == 0 && depth == 0 && P.tile_cnt != nullptr;
@@ -426,6 +347,8 @@
             off = rd.x * ld3(C.u) + rd.y * ld3(C.v);
             ray.tm = urange(loc, C.time0, C.time1);
           } else {
+            if constexpr (MF)
+              if (!cam_have) cam_e = P.S.cam_tab[s];  // the sample before this one ended in C: s < spp, the item goes on
             off = mk(cam_e.x, cam_e.y, cam_e.z);
             ray.tm = cam_e.w;
           }
@@ -462,36 +385,43 @@
           ray.tm = urange(cr, C.time0, C.time1);
           vset(att_r, 15, mk(1.0f, 1.0f, 1.0f));
         }
-        // traversal reciprocals: hardware v_rcp_f32 (1 ulp; the tree's boxes are padded by 2^-16
-        // relative, far above either reciprocal's rounding) instead of three IEEE divides
-        const V inv = mk(__builtin_amdgcn_rcpf(ray.d.x), __builtin_amdgcn_rcpf(ray.d.y), __builtin_amdgcn_rcpf(ray.d.z));
-        finv = mk(__builtin_fminf(__builtin_fmaxf(inv.x, -1e30f), 1e30f),
-                  __builtin_fminf(__builtin_fmaxf(inv.y, -1e30f), 1e30f),
-                  __builtin_fminf(__builtin_fmaxf(inv.z, -1e30f), 1e30f));
-        oi = mk(ray.o.x * finv.x, ray.o.y * finv.y, ray.o.z * finv.z);
-        qa = len2(ray.d);
-        rcpa = __builtin_amdgcn_rcpf(qa);
-        best = __builtin_inff();
-        bhi = __builtin_inff();
-        second = __builtin_inff();
-        best_prim = -1;
-        best_rank = 0x7fffffff;
-        cur = 0;
-        sp = 0;
-        overflow = false;
-        mode = 1;
+#include "rt_step_body_query.h"
         if constexpr ((F & F_WORLD) == 0) {
           if (listed && tcnt >= 0) {  // camera ray: the tile's candidate list instead of the tree
             tile_candidates<F>(S, ent, tcnt, g0, ray, qa, rcpa, tmin, tmax, best, bhi, second, best_prim, best_rank,
                                nprim);
             mode = 2;
+            RT_STEP_PASS_LANES(pass, 7, best_prim >= 0);
+            RT_STEP_PASS_LANES(pass, 8, best_prim < 0);
           }
         }
       }
-      if (pass + 1 >= kShadePasses || __ballot(mode == 2) == 0) break;
+      if constexpr (MF) {
+        // ---- C. the heavy block, once per pass: bounce hits, camera rays whose list holds a candidate,
+        // and the searches A declined (overflow; a world with entries after its BVH).  A camera ray whose
+        // list gave none is a certain miss: it keeps mode 2 for block A of the next phase and waits through
+        // the traversal loop as a listed camera ray does in the parent's order after the last pass.
+        // No ray is copied here or anywhere in the pass: a lane's ray is written in place by Q or by
+        // scatter ("the conditional ray copy").
+        RT_STAMP(5);
+        if (mode == 2 && !step_sure_miss(S, best_prim, overflow)) {
+#include "rt_step_body_heavy.h"
+        }
+        // ---- one pass per phase (rt_kernels.hip, at step_miss_first: more passes measured slower).  Left
+        // pending: those camera misses, and the paths that ended inside C (mode 0, not done: with an item
+        // whose next sample starts, or without one).
+        break;
+      } else {
+        if (pass + 1 >= kShadePasses || __ballot(mode == 2) == 0) break;
+      }
     }
     RT_STAMP(3);
-    if (__ballot(mode != 0) == 0) break;  // no item left for any lane of the wave (mode 2: a listed camera ray)
+    // Lanes a path's end in C left between queries (MF only: in the parent's order every lane leaves the
+    // passes traversing, waiting with mode 2, or done) wait through the traversal loop like mode 2 lanes.
+    // Wave-uniform and constant over the loop, which moves lanes from mode 1 to mode 2 only.
+    int wait0 = 0;
+    if constexpr (MF) wait0 = __popcll(__ballot(mode == 0 && !done));
+    if (__ballot(MF ? mode != 0 || !done : mode != 0) == 0) break;  // no item left for any lane of the wave (mode 2: a listed camera ray)
     // ---- traversal steps until shade_min lanes wait (or none traverses)
     for (;;) {
       RT_STEP_COUNT(3);
@@ -516,7 +446,7 @@
                        nprim);
         }
         // (the threshold as a kernel argument measured 1.5 % faster than the compile-time constant)
-        if (__ballot(mode == 1) == 0 || __popcll(__ballot(mode == 2)) >= P.shade_min) {
+        if (__ballot(mode == 1) == 0 || __popcll(__ballot(mode == 2)) + wait0 >= P.shade_min) {
           leaf_vote<F>(S, true, pend, 0, 0, ray, qa, rcpa, tmin, tmax, best, bhi, second, best_prim, best_rank,
                        nprim);
           break;
@@ -531,7 +461,7 @@
             mode = 2;
         }
         // (the threshold as a kernel argument measured 1.5 % faster than the compile-time constant)
-        if (__ballot(mode == 1) == 0 || __popcll(__ballot(mode == 2)) >= P.shade_min) break;
+        if (__ballot(mode == 1) == 0 || __popcll(__ballot(mode == 2)) + wait0 >= P.shade_min) break;
       }
     }
   }
